@@ -9,7 +9,7 @@ what `InferenceManager::Estep` does after `setParams` (src/inference_manager.cpp
 `split_ms.hmm_only_ms` additionally reports the same eval with the prepared parameters handed over by `set_raw`
 (no A6-A10), which is what round 1 timed.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|c2|c3|c4|c5|posterior|posterior64|posterior128|pbinned|qgrad|shaping] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline|c2|c3|c4|c5|posterior|posterior64|posterior128|pbinned|qgrad|shaping] [--no-cpu] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no torchrun environment re-launches itself under `torch.distributed.run` (one rank per
 GPU, RCCL); under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE.  Every rank owns one synthetic 100 Mbp contig
@@ -129,6 +129,55 @@ def gpu_power_state():
     return out or None
 
 
+DUMP_BUDGET = 64_000_000   # bytes `--dump-outputs` writes at most, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, suffix="", budget=DUMP_BUDGET):
+    """`--dump-outputs DIR`: every array as DIR/<name><suffix>.npy in float64 (float32 stays float32), so that two builds can be
+    compared output for output.  At most `budget` bytes in all: the arrays are written smallest first, and one larger than its
+    share of what is left keeps a fixed sample along its longest axis (seeded, sorted: columns of a posterior matrix, rows of a
+    contig), whose indices go beside it as <name>_index<suffix>.npy.  Returns what was written, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((k, np.asarray(v)) for k, v in arrays.items()), key=lambda kv: kv[1].nbytes)
+    left, files, sampled = budget, 0, []
+
+    def save(name, a):
+        nonlocal left, files
+        path = os.path.join(out_dir, name + suffix + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+        files += 1
+
+    for i, (name, a) in enumerate(items):
+        a = np.atleast_1d(a).astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        share = left // (len(items) - i) - 2 * 256          # (256: room for the .npy headers of the array and its index)
+        if a.nbytes > share:
+            ax = int(np.argmax(a.shape))
+            n = a.shape[ax]
+            k = max(1, min(n, share // (a.nbytes // n + 8)))
+            idx = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+            save(name + "_index", idx.astype(np.float64))
+            a = np.ascontiguousarray(np.take(a, idx, axis=ax))
+            sampled.append(name)
+        save(name, a)
+    assert left >= 0, "--dump-outputs exceeded its budget"
+    return {"dir": out_dir, "files": files, "bytes": budget - left, "sampled": sampled}
+
+
+def engine_outputs(top, im, ll):
+    """What a caller of the timed eval holds after its last step: the log-likelihood it returned, the per-contig log-likelihoods,
+    the key dictionary and the E-step's statistics per contig - xisum, the gamma sums in key order (zero where a contig lacks the
+    key) and gamma (the M x (L+1) posterior matrix with save_gamma, else its first column)."""
+    keys = im.keys
+    zero = np.zeros(im.M)
+    out = {"loglik": np.array([ll]), "logliks": np.asarray(top.logliks(), dtype=np.float64), "keys": keys,
+           "xisum": np.stack(im.xisums),
+           "gamma_sums": np.stack([[d.get(tuple(int(x) for x in k), zero) for k in keys] for d in im.gamma_sums])}
+    for c, g in enumerate(im.gammas):
+        out[f"gamma_{c}"] = g
+    return out
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a torchrun environment: start N ranks of this script."""
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
@@ -158,7 +207,11 @@ def main():
                     "for rocprofv3 passes, whose per-kernel totals must hold the default path only")
     ap.add_argument("--warm", action="store_true", help="additionally report the opt-in warm start (smcpp_set_warm_start) on a "
                     "trajectory of perturbed parameters; never part of `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed in its last step "
+                    "as DIR/<name>.npy (float64, at most 64 MB in all: a fixed sample of a larger output); N > 1: <name>_rank<r>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -341,6 +394,11 @@ def main():
             host_timings.append(im.last_host_timing())
     barrier()
     elapsed = time.perf_counter() - t0
+    # read back before anything below runs the manager again (reference width, hmm-only split, warm start)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, engine_outputs(top, im, ll), f"_rank{rank}" if world > 1 else "",
+                              DUMP_BUDGET // world)
     caller_ms = ({"set_model": 1e-6 * phase_ns[0] / phase_ns[3], "E_step": 1e-6 * phase_ns[1] / phase_ns[3],
                   "loglik": 1e-6 * phase_ns[2] / phase_ns[3],
                   "note": "mean wall clock of the three calls of an eval as the Python caller sees them; set_model holds the binding's "
@@ -723,6 +781,8 @@ def main():
             out["multi_gpu_check"] = multi_check
         if warm is not None:
             out["warm_start"] = warm
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world > 1:
             out["config"]["backend"] = "nccl (RCCL)" if backend == "nccl" else \
                 f"{backend}: {world} ranks share {ndev} device(s) - functional test of the N>1 path, not a measurement"
@@ -778,6 +838,7 @@ def bench_qgrad(args, im, model, a, s_, M, n, desc, host_threads, world, rank, t
         return val.copy(), jac.copy()
 
     per_call = []
+    last = {}
 
     def timed(steps, warmup):
         import gc
@@ -789,14 +850,15 @@ def bench_qgrad(args, im, model, a, s_, M, n, desc, host_threads, world, rank, t
         t0 = time.perf_counter()
         for i in range(steps):
             t1 = time.perf_counter()
-            one(i)
+            last["q"], last["jac"] = one(i)
             per_call.append(time.perf_counter() - t1)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / steps
 
-    steps = max(args.steps, 40)
+    steps = args.steps
     dev_s = timed(steps, args.warmup)
     dev_calls = sorted(per_call)
+    dumped = dump_outputs(args.dump_outputs, last) if args.dump_outputs else None
     rng = np.random.default_rng(5)
     v_dev, j_dev = one(0)
     im.set_prep_mode(True)
@@ -818,6 +880,8 @@ def bench_qgrad(args, im, model, a, s_, M, n, desc, host_threads, world, rank, t
                            "note": "`value` is steps / total time of the timed region; the spread of the individual calls is reported beside it"},
            "parity": {"val_rel_diff_max": float(np.max(np.abs(v_dev - v_host) / np.abs(v_host))),
                       "jac_rel_diff_max_per_term": [float(x) for x in np.max(np.abs(j_dev - j_host), axis=1) / sc]}}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     print(json.dumps(out), flush=True)
 
 
@@ -841,6 +905,7 @@ def bench_shaping(args, n, desc, world, rank, torch):
         out, k_ms = D.thin_bin_compress_device(raw, thinning, w, na, timing=True)
         walls.append(time.perf_counter() - t0)
         ms.append(k_ms)
+    dumped = dump_outputs(args.dump_outputs, {"rows": out}) if args.dump_outputs else None
     k_ms = float(np.median(ms))
     t, ms_t = D.thin_data_device(raw, thinning, timing=True)
     b, ms_b = D.bin_observations_device(t, w, na, timing=True)
@@ -873,6 +938,8 @@ def bench_shaping(args, n, desc, world, rank, torch):
                                       f"({Ppre} bp) in {host_s:.1f} s; the reference's compiled Cython cannot be built on the GPU box",
                             "identical_to_device_on_the_sample": bool(np.array_equal(c_host, c_dev))}}
     out["speedup_vs_cpu_1core"] = out["value"] / out["cpu_baseline"]["value"]
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     print(json.dumps(out), flush=True)
 
 

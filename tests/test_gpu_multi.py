@@ -101,15 +101,19 @@ def test_two_ranks_match_single_manager(tmp_path, disjoint, use_model):
         np.testing.assert_allclose(np.array(r[0]["jac"]), jac, rtol=1e-6, atol=1e-7 * np.abs(jac).max())
 
 
-def _exact_worker(rank, world, port, out_dir, backend):
-    """Two ranks; keeps the packed statistics before and after the all-reduce (gloo: ranks share device 0; nccl: one device each)."""
+def _exact_worker(rank, world, port, out_dir, backend, shared_device=False):
+    """Two ranks; keeps the packed statistics before and after the all-reduce (gloo: ranks share device 0; nccl: one device each,
+    or with `shared_device` both on device 0, each presenting itself to RCCL as a host of its own)."""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import torch
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    dev = rank if backend == "nccl" else 0
+    if shared_device:
+        # RCCL refuses two ranks of one host on one device; as two hosts they exchange over its socket transport (loopback)
+        os.environ.update(NCCL_HOSTID=f"smcpp-test-rank{rank}", NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1")
+    dev = rank if (backend == "nccl" and not shared_device) else 0
     torch.cuda.set_device(dev)
     dist.init_process_group(backend, rank=rank, world_size=world)
     from smcpp_amd import dist as sd
@@ -163,11 +167,12 @@ def test_reduction_is_exact_two_ranks_one_device(tmp_path):
 
 
 def test_reduction_is_exact_two_ranks_rccl(tmp_path):
-    """The same over RCCL (backend nccl), one rank per GPU: runs wherever two devices are visible (the 1-GPU test box skips)."""
+    """The same over RCCL (backend nccl), one rank per GPU.  With one visible GPU both ranks run on it as two RCCL hosts
+    (NCCL_HOSTID), so RCCL reduces over its socket transport instead of device to device; the engine's side - pack kernel into the
+    reduced tensor, all-reduce, unpack, and the engine's own RCCL communicator - is the same."""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two visible GPUs")
-    mp.spawn(_exact_worker, args=(2, _free_port(), str(tmp_path), "nccl"), nprocs=2, join=True)
+    shared = torch.cuda.device_count() < 2
+    mp.spawn(_exact_worker, args=(2, _free_port(), str(tmp_path), "nccl", shared), nprocs=2, join=True)
     _check_exact(tmp_path, 2)
     assert bool(np.load(tmp_path / "x0.npz")["nccl"])
     for i in range(2):
@@ -382,24 +387,27 @@ def test_bench_gpus_2_self_launches():
 
 @pytest.mark.parametrize("workload,extra", [("c3", []), ("c4", ["--length-mbp", "20"])])
 def test_bench_eight_ranks_dry_run(workload, extra):
-    """`bench.py --gpus 8 --workload c3 | c4 --check` as the driver launches it on an 8-GPU node, here with the eight ranks
-    sharing the one device over gloo (flagged in the output: a functional run, not a measurement): the contigs are partitioned,
-    every rank holds the same global key dictionary and - after the single all-reduce - bitwise the same Q; each rank's host
-    threads stay within its share of the CPU quota.  c3 = the 22 contigs of the whole genome LPT-sharded (strong scaling; also
-    checked against the compiled reference's recorded per-contig log-likelihoods, golden G16); c4 = two-population managers built
-    by ShardedInferenceManager's own factory."""
+    """`bench.py --gpus 8 --workload c3 | c4 --check` as the driver launches it on an 8-GPU node.  With fewer than eight devices
+    the ranks share them over gloo (flagged in the output: a functional run, not a measurement), and the run has four ranks: every
+    rank and this process hold the device open, and four keeps that to five processes on one device.  The contigs are
+    partitioned, every rank holds the same global key dictionary and - after the single all-reduce - bitwise the same Q; each
+    rank's host threads stay within its share of the CPU quota.  c3 = the 22 contigs of the whole genome LPT-sharded (strong
+    scaling; also checked against the compiled reference's recorded per-contig log-likelihoods, golden G16); c4 =
+    two-population managers built by ShardedInferenceManager's own factory, one contig per rank."""
+    import torch
+    ranks = 8 if torch.cuda.device_count() >= 8 else 4
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", workload, "--steps", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--workload", workload, "--steps", "2",
                         "--warmup", "1", "--no-cpu", "--check"] + extra, capture_output=True, text=True, env=env, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
-    assert out["n_gpus"] == 8 and out["value"] > 0
+    assert out["n_gpus"] == ranks and out["value"] > 0
     mc = out["multi_gpu_check"]
-    assert mc["ranks"] == 8 and mc["q_bitwise_identical"]
-    assert all(1 <= t <= max(1, mc["cpu_quota"] // 8) for t in mc["host_threads_per_rank"])
-    assert sorted(c for r in mc["contigs_per_rank"] for c in r) == list(range(22 if workload == "c3" else 8))
+    assert mc["ranks"] == ranks and mc["q_bitwise_identical"]
+    assert all(1 <= t <= max(1, mc["cpu_quota"] // ranks) for t in mc["host_threads_per_rank"])
+    assert sorted(c for r in mc["contigs_per_rank"] for c in r) == list(range(22 if workload == "c3" else ranks))
     if workload == "c3":
         assert out["scaling"] == "strong" and abs(out["parity_full_size"]["rel_diff"]) <= 1e-6
     else:

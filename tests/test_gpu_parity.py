@@ -713,16 +713,17 @@ def test_em_on_the_reference_example_pipeline():
 def test_c5_slice_5000_rows_vs_compiled_reference(chain_family):
     """Golden G14 (tests/golden/make_golden_c5.py): config C5 (M = 256, n = 50) on the first 5 000 rows of its contig, outputs of
     the compiled reference; several chunks, so the chunk-parallel iteration (scan chains with 4 states per lane by default,
-    streamed-operand chains with `dense`) is exercised at this state count."""
+    streamed-operand chains with `dense`, and with `lock`: the lock-step chains exist for M <= 64 only, so forcing them at this
+    state count must leave the manager on the streamed-operand chains) is exercised at this state count."""
     import os
     from conftest import ROOT
     from smcpp_amd import _smcpp
-    if chain_family == "lock":
-        pytest.skip("lock-step chains exist for M <= 64")
     p = dict(np.load(os.path.join(ROOT, "tests", "golden", "params_M256_n50.npz")))
     g = load_golden("G14_c5_slice")
     obs = np.ascontiguousarray(g["obs"], dtype=np.int32)
     im = _smcpp.PyOnePopInferenceManager(50, [obs], p["hs"], ("pop1",), float(p["pol"]))
+    if chain_family in ("lock", "dense"):
+        assert im.chain_mode() == 3
     im.theta = float(p["theta"]); im.rho = float(p["rho"]); im.alpha = float(p["alpha"])
     im.set_raw(p["pi"], p["T"], p["keys"], p["E"])
     im.set_chunking(700)

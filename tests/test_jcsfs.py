@@ -14,7 +14,8 @@ import os
 import numpy as np
 import pytest
 
-from oracle import prep_oracle, ref
+from conftest import load_golden
+from oracle import prep_oracle
 from smcpp_amd import _engine as E, _smcpp
 from smcpp_amd.model import PiecewiseModel, TwoPopulationModel
 
@@ -190,19 +191,19 @@ def test_apart_matches_golden_from_compiled_reference_pieces():
         assert np.all(J[:, 0, 0, 0, 0] == 0) and np.all(J[:, 1, n1, 1, n2] == 0)
 
 
-@pytest.mark.skipif(not ref.available(), reason="compiled reference (oracle/_ref) not built")
 def test_apart_matches_live_oracle_on_other_models():
-    from oracle import jcsfs_apart_oracle as JA
+    """oracle/jcsfs_apart_oracle.py (the compiled reference's building blocks) on six more models, recorded with their inputs
+    in golden G25 (tests/golden/make_golden_reference_live.py)."""
     from smcpp_amd import _engine
-    rng = np.random.default_rng(5)
-    for n1, n2 in ((2, 7), (5, 1)):
-        a1 = np.exp(rng.normal(0, 0.7, 5)); a2 = np.exp(rng.normal(0, 0.7, 3))
-        s1 = np.exp(rng.normal(-2, 0.8, 5)); s2 = np.exp(rng.normal(-2, 0.8, 3))
-        hs = np.r_[0.0, np.sort(np.exp(rng.normal(-1.5, 1.2, 7))), np.inf]
-        for split in (0.0, float(hs[2]), 0.33):
-            J = _engine.host_joint_csfs(n1, n2, 1, 1, hs, (a1, s1), (a2, s2), split)
-            R = JA.joint_csfs_apart(n1, n2, hs, (a1, s1), (a2, s2), split)
-            np.testing.assert_allclose(J, R, rtol=1e-10, atol=5e-15)
+    g = load_golden("G25_reference_live")
+    assert int(g["apart_ncases"]) == 6
+    for i in range(int(g["apart_ncases"])):
+        n1, n2 = (int(x) for x in g[f"apart{i}_n"])
+        a1, s1, a2, s2, hs = (g[f"apart{i}_{k}"] for k in ("a1", "s1", "a2", "s2", "hs"))
+        split = float(g[f"apart{i}_split"])
+        J = _engine.host_joint_csfs(n1, n2, 1, 1, hs, (a1, s1), (a2, s2), split)
+        R = g[f"apart{i}_J"]
+        np.testing.assert_allclose(J, R, rtol=1e-10, atol=5e-15)
 
 
 def test_c4_real_shape_parameters_match_reference_fixture():

@@ -1,10 +1,18 @@
 """Host-side cold preparation (smcpp_amd/csrc/prep.hpp) against the parameter files the
-compiled reference emitted (tests/golden/params_*.npz, G*.npz) and, in the build container, the compiled reference live."""
+compiled reference emitted (tests/golden/params_*.npz, G*.npz; G25 = its `ref_prep` / `ref_prep_jac` answers at further sizes)."""
 import numpy as np
 import pytest
 
 from conftest import load_golden
-from oracle import prep_oracle, ref
+from oracle import prep_oracle
+
+
+def _reference(kind, M, n):
+    """The compiled reference's recorded answer for size (M, n) (golden G25, tests/golden/make_golden_reference_live.py)."""
+    g = load_golden("G25_reference_live")
+    i = next(i for i in range(16) if f"{kind}{i}_M" in g and (int(g[f"{kind}{i}_M"]), int(g[f"{kind}{i}_n"])) == (M, n))
+    p = f"{kind}{i}_"
+    return {k[len(p):]: v for k, v in g.items() if k.startswith(p)}
 
 
 def _prep(g, keys=None):
@@ -100,14 +108,14 @@ def test_factored_csfs_equals_literal(M, n, nder):
         np.testing.assert_allclose(fast[5], lit[5], rtol=1e-9, atol=1e-14 * max(1.0, np.abs(lit[5]).max()))
 
 
-@pytest.mark.skipif(not ref.available(), reason="compiled reference (oracle/_ref) not built")
 @pytest.mark.parametrize("M,n", [(8, 0), (8, 1), (8, 2), (24, 3), (51, 28)])
 def test_prep_vs_reference_live_edge_sizes(M, n):
     from smcpp_amd import _engine
     hs = np.r_[0., np.logspace(-2, 1, M - 1), np.inf]
     a = np.array([1.0, 2.0, 0.5, 1.0, 3.0]); s = np.array([0.05, 0.2, 1.0, 1.0, 1.0])
     theta, rho, alpha, pol = 2.5e-2, 6e-3, 1.0, 0.3
-    p = ref.prep(a, s, hs, rho, theta, n)
+    p = _reference("edge", M, n)                       # `ref_prep(a, s, hs, rho, theta, n)`
+    assert np.array_equal(p["hs"], hs) and np.array_equal(p["a"], a) and np.array_equal(p["s"], s)
     keys = [[0, 0, 0], [1, 0, 0], [-1, 0, 0]]
     if n > 0:
         keys += [[0, b, n] for b in range(1, n + 1)] + [[1, b, n] for b in range(0, n + 1)]
@@ -137,7 +145,6 @@ def test_known_answers_constant_size():
     np.testing.assert_allclose(E[0] + E[1], 1.0, rtol=1e-13)             # reduced keys: exp(-2 a theta E[T]) and complement
 
 
-@pytest.mark.skipif(not ref.available(), reason="compiled reference (oracle/_ref) not built")
 @pytest.mark.parametrize("M,n", [(8, 3), (32, 10)])
 def test_jacobians_vs_reference_autodiff(M, n):
     """Forward-mode duals through rows A7-A10 against the reference's AutoDiffScalar (adouble) derivatives."""
@@ -146,7 +153,8 @@ def test_jacobians_vs_reference_autodiff(M, n):
     a, s = synth.model_pieces(6)
     da = np.eye(6)[:, :4] + 0.25                       # arbitrary non-trivial seed matrix, nder = 4
     theta, rho, alpha, pol = 2.5e-2, 6.25e-3, 1.0, 0.5
-    r = ref.prep_jac(a, da, s, hs, rho, theta, n)
+    r = _reference("jac", M, n)                        # `ref_prep_jac(a, da, s, hs, rho, theta, n)`
+    assert np.array_equal(r["hs"], hs) and np.array_equal(r["a"], a) and np.array_equal(r["s"], s) and np.array_equal(r["da"], da)
     keys = np.array(sorted({(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, n), (1, 0, n), (1, n, n), (2, 1, n), (0, 1, n - 1)}),
                     dtype=np.int32)
     pi, T, E, dpi, dT, dE = _engine.host_prep_onepop_jac(n, hs, pol, a, da, s, theta, rho, alpha, keys)
