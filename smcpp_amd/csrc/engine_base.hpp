@@ -86,7 +86,7 @@ struct DevBuf {
         n = count;
         if (count) {
             HIPCHK(hipMalloc((void **)&p, count * sizeof(T)));
-            smcpp_opt::poison(p, count * sizeof(T), line, file);
+            smcpp_opt::poison(p, count * sizeof(T), line, file, std::is_floating_point<T>::value);
         }
     }
     void free() {
@@ -255,7 +255,7 @@ struct DevPrep {
                 if (d_in) (void)hipFree(d_in);
                 in_cap = bytes + bytes / 2;
                 HIPCHK(hipMalloc((void **)&d_in, in_cap));
-                smcpp_opt::poison(d_in, in_cap, __LINE__, __FILE__);
+                smcpp_opt::poison(d_in, in_cap, __LINE__, __FILE__, false);     // (doubles, then the int indices hsi: not all floating)
             }
         }
         double *hd = reinterpret_cast<double *>(hb);
@@ -423,7 +423,7 @@ struct TwoPopDevCsfs : smcpp_host::CsfsBatchDevice {
             if (I.d_in) (void)hipFree(I.d_in);
             I.in_cap = bytes + bytes / 2;
             HIPCHK(hipMalloc((void **)&I.d_in, I.in_cap));
-            smcpp_opt::poison(I.d_in, I.in_cap, __LINE__, __FILE__);
+            smcpp_opt::poison(I.d_in, I.in_cap, __LINE__, __FILE__, false);  // (doubles, then the int indices hsi: not all floating)
         }
         double *hd = reinterpret_cast<double *>(hb);
         size_t o = 0;

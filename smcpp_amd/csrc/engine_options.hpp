@@ -68,7 +68,9 @@ static const OptDef OPT_DEFS[O_COUNT] = {
     {"SMCPP_SPLIT_SPANS",    "0: rows of binned data longer than 64 positions are not cut into pieces (M > 64); 2: un-binned rows are cut as well at M <= 256 (test switch)"},
     {"SMCPP_T_LAZY",         "0: the model path expands the M x M transition matrix before the chains start and takes their generators from it (rounds 3-5)"},
     {"SMCPP_DEBUG_POISON",   "byte value every fresh device allocation is filled with (255: NaN / -1): a kernel that reads memory it was "
-                             "never given shows up as NaN in a fresh process instead of depending on what the allocator recycles"},
+                             "never given shows up as NaN in a fresh process instead of depending on what the allocator recycles; "
+                             "nan: 0xFF only in allocations of float / double data (integer buffers untouched), and the parameter "
+                             "arena and the per-row posteriors are poisoned again in stream order on every E-step (tests/test_gpu_poison.py)"},
     {"SMCPP_DEBUG_POISON_ONLY", "poison only the allocation with this index (counted from the last smcpp_reload_options): tools/poison_probe.py"},
     {"SMCPP_DEBUG_POISON_LOG",  "set: print index, source line and size of every device allocation to stderr"},
 };
@@ -80,6 +82,7 @@ struct EngineOptions {
     long long ival_[O_COUNT];
     double dval_[O_COUNT];
     unsigned generation = 0;
+    bool poison_nan = false;          // SMCPP_DEBUG_POISON=nan (see poison() below)
     void parse() {
         for (int k = 0; k < O_COUNT; ++k) {
             const char *e = getenv(OPT_DEFS[k].name);
@@ -88,6 +91,7 @@ struct EngineOptions {
             ival_[k] = e ? strtoll(e, nullptr, 0) : 0;
             dval_[k] = e ? atof(e) : 0.0;
         }
+        poison_nan = is(O_DEBUG_POISON, "nan");
         ++generation;
     }
     bool has(OptId k) const { return set_[k]; }
@@ -112,13 +116,20 @@ inline int &alloc_counter() { static int c = 0; return c; }
 inline void reload() { options_mut().parse(); alloc_counter() = 0; }
 // Debug aid (SMCPP_DEBUG_POISON): fill a FRESH device allocation with a byte pattern.  hipMalloc hands out zeroed pages in a fresh
 // process and recycled ones later; a kernel that reads memory nobody wrote is correct in the first case only by accident.
+// `floating`: the allocation holds float / double data only.  SMCPP_DEBUG_POISON=nan fills just those (0xFF bytes are NaN in both
+// widths) and leaves integer buffers alone: they hold indices, row counts, tile and piece lists and cross-workgroup flags, where -1
+// could become an address out of range or a wait that never ends - the mode the test suite runs.  The numeric mode fills everything.
 inline void poison_fill(void *p, size_t bytes, int value) { (void)hipMemset(p, value, bytes); (void)hipDeviceSynchronize(); }
-inline void poison(void *p, size_t bytes, int line, const char *file) {
+inline void poison(void *p, size_t bytes, int line, const char *file, bool floating) {
     const EngineOptions &o = opt();
     const int idx = alloc_counter()++;
-    if (o.has(O_DEBUG_POISON_LOG)) fprintf(stderr, "[alloc %d] %s:%d %zu bytes\n", idx, file, line, bytes);
+    if (o.has(O_DEBUG_POISON_LOG)) fprintf(stderr, "[alloc %d] %s:%d %zu bytes%s\n", idx, file, line, bytes, floating ? "" : " (integer)");
     if (!o.has(O_DEBUG_POISON) || !p || !bytes) return;
     if (o.has(O_DEBUG_POISON_ONLY) && o.i(O_DEBUG_POISON_ONLY, -1) != idx) return;
+    if (o.poison_nan) {
+        if (floating) poison_fill(p, bytes, 0xff);
+        return;
+    }
     poison_fill(p, bytes, o.i(O_DEBUG_POISON, 255) & 0xff);
 }
 

@@ -285,7 +285,7 @@ bool smcpp_im::q_device(double val[4], double *jac) {
         if (q.d_in) (void)hipFree(q.d_in);
         q.in_cap = ndbl * sizeof(double) * 2;
         HIPCHK(hipMalloc((void **)&q.d_in, q.in_cap));
-        smcpp_opt::poison(q.d_in, q.in_cap, __LINE__, __FILE__);
+        smcpp_opt::poison(q.d_in, q.in_cap, __LINE__, __FILE__, true);       // (doubles only)
     }
     double *hb = reinterpret_cast<double *>(q.stage.base);
     for (int i = 0; i < M; ++i) {
@@ -554,7 +554,7 @@ void smcpp_im::host_prep_and_upload() {
         if (d_param) (void)hipFree(d_param);
         param_cap = need + need / 4;
         HIPCHK(hipMalloc((void **)&d_param, param_cap));
-        smcpp_opt::poison(d_param, param_cap, __LINE__, __FILE__);
+        smcpp_opt::poison(d_param, param_cap, __LINE__, __FILE__, true);     // (float / double arrays only, see the places below)
     }
     size_t off = 0;
     char *hb = stage.base;
@@ -576,6 +576,9 @@ void smcpp_im::host_prep_and_upload() {
     if (off > need) throw std::runtime_error("internal: parameter arena overflow");
     auto tp2 = std::chrono::steady_clock::now();
     arena_side = lean && stream2 != nullptr && dual_stream;
+    // SMCPP_DEBUG_POISON=nan: the whole arena is NaN again in front of its copy, on the copy's stream - a consumer that waits for the
+    // copy sees this E-step's parameters, one that races it NaN instead of the previous E-step's plausible ones
+    if (opt().poison_nan) HIPCHK(hipMemsetAsync(d_param, 0xff, param_cap, arena_side ? stream2 : s));
     if (arena_side) {
         // nothing the chains read lives in this arena: the copy runs beside them, the statistics wait for it
         HIPCHK(hipMemcpyAsync(d_param, hb, off, hipMemcpyHostToDevice, stream2));

@@ -176,7 +176,7 @@ void smcpp_im::stage_static_and_prepass() {
         if (d_pre) (void)hipFree(d_pre);
         pre_cap = need + need / 4;
         HIPCHK(hipMalloc((void **)&d_pre, pre_cap));
-        smcpp_opt::poison(d_pre, pre_cap, __LINE__, __FILE__);
+        smcpp_opt::poison(d_pre, pre_cap, __LINE__, __FILE__, true);         // (float / double arrays only)
     }
     size_t off = 0;
     auto put = [&](const void *src, size_t bytes) {
@@ -576,7 +576,7 @@ void smcpp_im::ss_launch_initial() {
         if (d_pre) (void)hipFree(d_pre);
         pre_cap = need + need / 4;
         HIPCHK(hipMalloc((void **)&d_pre, pre_cap));
-        smcpp_opt::poison(d_pre, pre_cap, __LINE__, __FILE__);
+        smcpp_opt::poison(d_pre, pre_cap, __LINE__, __FILE__, true);         // (float / double arrays only)
     }
     size_t off = 0;
     auto put = [&](const void *src, size_t bytes) {
@@ -1349,6 +1349,14 @@ void smcpp_im::estep() {
     host_timing[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if ((int)pi.size() != M || (!T_lazy && (int)T.size() != M * M) || (!E_on_dev && (int)E.size() != K * M))
         throw std::runtime_error("parameters are not set");
+    if (opt().poison_nan && save_gamma) {
+        // SMCPP_DEBUG_POISON=nan: the per-row posteriors (padding columns included) are NaN again on every save_gamma E-step - on the
+        // main stream in front of everything this E-step enqueues, not behind the chains' fork event (the round-6 race below,
+        // enqueue_stats): a row or column no statistics kernel writes shows up as NaN instead of as the previous E-step's value.
+        // Row 0 of each contig is cleared again by enqueue_stats.
+        d_gamma_rows.alloc((size_t)total_rows * Mp);
+        HIPCHK(hipMemsetAsync(d_gamma_rows.p, 0xff, sizeof(double) * d_gamma_rows.n, stream));
+    }
     HIPCHK(hipEventRecord(ev[0], stream));
     // span > 1 rows without an eigensystem (kernels.hpp: k_span_fold): the span is expanded by smax steps of two M x M products
     const bool eigfree_off = opt().off(smcpp_opt::O_EIGFREE);

@@ -132,8 +132,10 @@ __device__ __forceinline__ ThinGeom thin_geom(long long start, long long span, l
     g.head = g.first > 1 ? 1 : 0;
     return g;
 }
+// a row without a kept position is one thinned row - unless its span is 0 (then rem = 0): the reference's `while span > 0` emits
+// nothing for it, and neither does this (k_thin_emit never sees such a row: its range of outputs is empty)
 __device__ __forceinline__ long long thin_count(const ThinGeom &g, long long thinning) {
-    if (g.kept == 0) return 1;
+    if (g.kept == 0) return g.rem > 0 ? 1 : 0;
     return g.head + 1 + (g.kept - 1) * ((thinning > 1 ? 1 : 0) + 1) + (g.rem > 0 ? 1 : 0);
 }
 struct SpanOf {

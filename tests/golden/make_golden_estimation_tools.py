@@ -94,6 +94,16 @@ def main():
     small[small[:, 1] == -1, 2:] = 0
     small[::7, 2] = small[::7, 3]                    # b == nb on some rows (the "nonseg" branch when a == 2)
     inputs["small"] = (small, [2])
+    # zero-span rows (the short-span mix again, its own seed): at the first row, at the last row, two in a row, and one in every 37
+    # rows, i.e. inside thinning windows at every phase - `thin_data` emits nothing for them (`while span > 0`), `process_bin` skips
+    # them.  Only thin_data / bin_observations run on this input (the operations with a device form, shaping.hpp)
+    zs = rng.integers(0, 100, (600, 1))
+    zspan = np.concatenate([rng.integers(1, 40, (600, 1)), np.where(zs < 5, -1, np.where(zs < 12, 2, np.where(zs < 30, 1, 0))),
+                            rng.integers(0, 7, (600, 1)), np.full((600, 1), 6)], axis=1).astype(np.int32)
+    zspan[zspan[:, 1] == -1, 2:] = 0
+    zspan[[0, 100, 101, 599], 0] = 0
+    zspan[::37, 0] = 0
+    zspan_ops = {"thin": ((1, 0), (7, 0), (7, 3), (40, 0), (40, 13), (400, 0)), "bin": (10, 50)}
     out = {}
     for name, (data, a) in inputs.items():
         out[f"{name}_in"] = data
@@ -114,6 +124,13 @@ def main():
         # the pipeline's own composition (data_filter.py:166-203: Thin, then Bin on the thinned rows)
         t = ref.thin_data(data.copy(), 400, 0)
         out[f"{name}_thin400_bin100"] = ref.bin_observations(C(t, a), 1000 if big else 100)
+    out["zspan_in"] = zspan
+    out["zspan_a"] = np.array([2], dtype=np.int64)
+    for th, off in zspan_ops["thin"]:
+        out[f"zspan_thin_{th}_{off}"] = ref.thin_data(zspan.copy(), th, off)
+    for w in zspan_ops["bin"]:
+        out[f"zspan_bin_{w}"] = ref.bin_observations(C(zspan.copy(), [2]), w)
+    out["zspan_thin400_bin100"] = ref.bin_observations(C(ref.thin_data(zspan.copy(), 400, 0), [2]), 100)
     # outputs on un-binned data run to millions of rows: beyond 64 KB an output is stored as its shape, the CRC-32 of its bytes
     # (int32, C order) and its first and last 500 rows - the comparison is bit-exact either way
     import zlib

@@ -361,11 +361,12 @@ def test_thin_bin_realign_window_counts_vs_the_reference_cython():
     """SURVEY.md 8 f-2, pinned BY EXECUTION since round 6 (golden G23, tests/golden/make_golden_estimation_tools.py): the reference's
     own `smcpp/_estimation_tools.pyx` - its text of `thin_data` (8-84), `bin_observations` (146-173), `realign` (176-209) and
     `windowed_mutation_counts` (212-255), compiled in the build container with the one GSL-dependent function left out - run on the
-    example-derived contig, on the reference's un-binned test contig test/bugs/11, on seven-column two-population rows and on a
-    short-span mix; `smcpp_amd.data` must reproduce every output row for row, bit for bit."""
+    example-derived contig, on the reference's un-binned test contig test/bugs/11, on seven-column two-population rows, on a
+    short-span mix and on rows of span 0 (first, last, two in a row, inside thinning windows: thin / bin only); `smcpp_amd.data`
+    must reproduce every output row for row, bit for bit."""
     z, names = _g23_cases()
     n_checked = 0
-    for inp in ("ex", "chr11", "twopop", "small"):
+    for inp in ("ex", "chr11", "twopop", "small", "zspan"):
         raw = np.ascontiguousarray(z[inp + "_in"], dtype=np.int32)
         a = [int(x) for x in z[inp + "_a"]]
         npop = (raw.shape[1] - 1) // 3

@@ -35,7 +35,7 @@ def test_thin_and_bin_on_the_device_vs_the_reference_cython():
     z = np.load(os.path.join(GOLDEN, "G23_estimation_tools.npz"))
     names = sorted({k.split("__")[0] for k in z.files})
     n = 0
-    for inp in ("ex", "chr11", "twopop", "small"):
+    for inp in ("ex", "chr11", "twopop", "small", "zspan"):
         raw = np.ascontiguousarray(z[inp + "_in"], dtype=np.int32)
         a = [int(x) for x in z[inp + "_a"]]
         for key in names:
@@ -84,6 +84,17 @@ def test_pipeline_on_the_device_vs_the_host_implementation():
     small = raw[:3000].copy(); small[:, 0] = np.minimum(small[:, 0], 37)
     for thinning, off in ((1, 0), (7, 3), (5, 9)):
         assert np.array_equal(D.thin_data_device(small, thinning, off), D.thin_data(small, thinning, off)), (thinning, off)
+    # rows of span 0 (first, last, two in a row, scattered): thinning emits nothing for them, so every later row keeps its place
+    for rows, thinning, off, w in ((raw, 400, 0, 100), (small, 7, 0, 10), (small, 7, 3, 10), (small, 1, 0, 10)):
+        z = rows.copy()
+        z[[0, 1, 500, 501, len(z) - 1], 0] = 0
+        z[::97, 0] = 0
+        t_h = D.thin_data(z, thinning, off)
+        assert np.all(t_h[:, 0] > 0)
+        assert np.array_equal(D.thin_data_device(z, thinning, off), t_h), (thinning, off)
+        if off == 0:
+            c_h = D.compress_repeated_obs(D.bin_observations(t_h, w, [2]))
+            assert np.array_equal(D.thin_bin_compress_device(z, thinning, w, [2]), c_h), thinning
 
 
 def test_pipeline_properties_at_a_million_rows():
