@@ -9,6 +9,9 @@
                       L-BFGS-B on -Q with the engine's gradients) with the plugins that change results:
                       LoglikelihoodMonitor (plugins/loglikelihood_monitor.py), ParameterOptimizer for rho
                       (plugins/parameter_optimizer.py), AnalysisSaver (plugins/analysis_saver.py)
+  SMCTwoPopulationModel smcpp/model.py:260-333 — two SMCModels and the split time
+  SplitAnalysis       smcpp/analysis/split.py + smcpp/commands/split.py — split-time estimation from two marginal fits,
+                      one manager per population tuple at ONE hidden state, `dump()` = model.final.json
 
 Host-side Python like the reference's; every likelihood evaluation runs on the GPU through `smcpp_amd._smcpp`.
 Derivatives: the model hands the engine the seed matrix d a_k / d y_j of its pieces with respect to the optimised
@@ -134,6 +137,142 @@ class SMCModel(Observable):
         r._y[:] = d["y"]
         return r
 
+
+class SMCTwoPopulationModel(Observable):
+    """`SMCTwoPopulationModel` (smcpp/model.py:260-333): population 1's `SMCModel` `model1`, population 2's `model2` and the
+    `split` time (coalescent units).  `for_pop(pid)` is what the inference managers read:
+
+      None          the distinguished model of a manager whose two distinguished lineages sit in different populations:
+                    model1's pieces with the split inserted, an infinite first piece of length `split` (no coalescence before it)
+      model1.pid    model1 itself
+      model2.pid    a NEW `SMCModel` on the merged knots unique(sort([knots1, knots2, split])): log model2 below the split,
+                    log model1(split) on it, log model1 above it - re-evaluated on `PIECES` log-spaced pieces of its own
+
+    (`smcpp_amd.model.TwoPopulationModel` is a different construction over fixed pieces and stays as it is.)"""
+    NPOP = 2
+
+    def __init__(self, model1, model2, split):
+        super().__init__()
+        self._models = [model1, model2]
+        model1.register(self)
+        model2.register(self)
+        self._split = split
+
+    @property
+    def model1(self):
+        return self._models[0]
+
+    @property
+    def model2(self):
+        return self._models[1]
+
+    @property
+    def pids(self):
+        return [m.pid for m in self._models]
+
+    @property
+    def N0(self):
+        assert self.model1.N0 == self.model2.N0
+        return self.model1.N0
+
+    @property
+    def K(self):
+        return self.model1.K
+
+    @property
+    def s(self):
+        return self.model1.s
+
+    @property
+    def distinguished_model(self):
+        return self.model1
+
+    @property
+    def dlist(self):
+        return self.model1.dlist + self.model2.dlist
+
+    @property
+    def split(self):
+        return self._split
+
+    @split.setter
+    def split(self, x):
+        self._split = x
+        self.update_observers("model update")
+
+    @property
+    def split_ind(self):
+        """k such that model2.knots[k] <= split < model2.knots[k + 1]."""
+        return np.searchsorted(self.model2.knots, self._split, side="right") - 1
+
+    def update(self, message, *args, **kwargs):
+        # changes of either population's model propagate to whoever observes the pair
+        self.update_observers("model update")
+
+    def for_pop(self, pid):
+        from .model import _Pieces
+        if pid is None:
+            m1 = self.model1
+            cs = np.concatenate([[0.0], np.cumsum(m1.s)])
+            cs[-1] = np.inf
+            ip = np.searchsorted(cs, self._split)
+            sp = np.diff(np.insert(cs, ip, self._split))
+            sp[-1] = 1.0
+            s = sp[ip - 1:]
+            s[0] = self._split
+            a = np.insert(m1.stepwise_values()[ip - 1:], 0, np.inf)
+            return _Pieces(a, s)
+        i = self.pids.index(pid)
+        if i == 0:
+            return self.model1
+        assert self.model1.N0 == self.model2.N0
+        kts = np.unique(np.sort(np.r_[self.model1.knots, self.model2.knots, self._split]))
+        i = np.searchsorted(kts, self._split)
+        m = SMCModel(kts, self.model1.N0, self.model2.pid)
+        y = np.empty(len(kts))
+        y[:i] = np.log(self.model2(kts[:i]))
+        y[i] = np.log(self.model1(self._split).item())
+        y[i + 1:] = np.log(self.model1(kts[i + 1:]))
+        m._y[:] = y
+        return m
+
+    def regularizer(self):
+        # (the reference's FIXME: the part before the split is counted twice)
+        return sum(self.for_pop(pid).regularizer() for pid in self.pids)
+
+    def __getitem__(self, coords):
+        """`[:]`: model1's coordinates followed by model2's; `[(i, cc)]`: coordinates `cc` of model i."""
+        if isinstance(coords, slice):
+            if coords != slice(None, None, None):
+                raise RuntimeError("only the full slice is supported")
+            return np.concatenate([self.model1[:], self.model2[:]])
+        a, cc = coords
+        return self._models[a][cc]
+
+    def __setitem__(self, coords, x):
+        if isinstance(coords, slice):
+            if coords != slice(None, None, None):
+                raise RuntimeError("only the full slice is supported")
+            k = len(self.model1)
+            self.model1[:] = x[:k]
+            self.model2[:] = x[k:]
+            return
+        a, cc = coords
+        self._models[a][cc] = x
+
+    def to_dict(self):
+        return {"class": "SMCTwoPopulationModel", "model1": self.model1.to_dict(), "model2": self.model2.to_dict(),
+                "split": float(self._split)}
+
+    @classmethod
+    def from_dict(cls, d):
+        assert d["class"] == "SMCTwoPopulationModel"
+        return cls(SMCModel.from_dict(d["model1"]), SMCModel.from_dict(d["model2"]), d["split"])
+
+
+def model_from_dict(d):
+    """The model of a `model.final.json` (its "model" entry), whichever class wrote it (base.py `_model_cls_d`)."""
+    return {"SMCModel": SMCModel, "SMCTwoPopulationModel": SMCTwoPopulationModel}[d["class"]].from_dict(d)
 
 @dataclass
 class EstimateArgs:
@@ -444,6 +583,201 @@ class Analysis:
         """`model.final.json` (base.py:186-191)."""
         write_final_json(filename, self._theta, self._rho, self._alpha, self._model, {self.populations[0]: self.hidden_states})
 
+
+@dataclass
+class SplitArgs:
+    """The options of `smc++ split` that reach SplitAnalysis (smcpp/commands/split.py): the two marginal fits `pop1` / `pop2`
+    (paths of their `.final.json` files, or the loaded dicts) and the data options of an estimation command.  mu and rho are
+    not options: mu = theta / (2 N0) of pop1's fit, r = None (split.py:41-43)."""
+    pop1: object = None
+    pop2: object = None
+    polarization_error: float = 0.5
+    unfold: bool = False
+    nonseg_cutoff: Optional[int] = None
+    outdir: Optional[str] = None
+    base: str = "model"
+    cores: Optional[int] = None
+    device: int = -1
+
+
+def _load_final(x):
+    if isinstance(x, dict):
+        return x
+    with open(x, "rt") as f:
+        return json.load(f)
+
+
+class SplitAnalysis:
+    """Split-time estimation from two marginal fits (smcpp/analysis/split.py on smcpp/analysis/base.py), `smc++ split`.
+    `contigs`: `smcpp_amd.data.Contig`s or paths of .smc(.gz) files, one- and two-population data sets mixed.
+
+    The model is `SMCTwoPopulationModel(model1, model2, max_split / 2)` with max_split = model2's last knot; every inference
+    manager - one per population tuple `pid` of the data - has the hidden states [0, inf] (M = 1).  `run()` is ONE EM
+    iteration of `TwoPopulationOptimizer`, which has no coordinate groups, so what changes the model are the observers of
+    its "pre M-step" event.  Of the plugins `SMCPPOptimizer.__init__` registers (every enabled `OptimizerPlugin` subclass
+    with a null constructor: AsciiPlotter, Debugger, HiddenStateOccupancyPrinter, LoglikelihoodMonitor, ProgressPrinter,
+    ScaleOptimizer) plus the split's `ParameterOptimizer("split", (0, max_split), "model")`, two act on "pre M-step":
+
+      1. ParameterOptimizer: bounded scalar search of the split on (0, max_split) minimising -Q (scipy's default xatol);
+      2. ScaleOptimizer: bounded scalar search of one common shift in (-1, 1) of ALL log sizes, model1's and model2's.
+
+    The others only log (LoglikelihoodMonitor could stop a second iteration; there is none).  The reference keeps the
+    observers in a WeakSet, whose order follows object addresses; in repeated runs of the reference's own optimizer
+    classes under CPython the split plugin came before ScaleOptimizer every time, and that is the order here.  Q is the sum
+    of `Q(separate=True)` over the managers (the regularisation penalty is 0)."""
+
+    def __init__(self, contigs, args: SplitArgs):
+        self._args = args
+        if args.cores is not None:
+            _smcpp.set_num_threads(args.cores)
+        d1, d2 = _load_final(args.pop1), _load_final(args.pop2)
+        # ---- split.py:40-43 + base.py:24-47 ----
+        mu = d1["theta"] / (2.0 * d1["model"]["N0"])
+        self._N0 = 0.5e-4 / mu
+        self._theta = 2.0 * self._N0 * mu
+        self._rho = self._theta
+        self._penalty = 0.0
+        self._niter = 1
+        self._pol = 0.0 if args.unfold else args.polarization_error
+        # ---- base.py:49-61 without thinning / binning ----
+        cs = [D.load_smc(c) if isinstance(c, str) else c for c in contigs]
+        pops = []
+        for c in cs:
+            pops += [p for p in c.pid if p not in pops]
+        if len(pops) > 2:
+            raise RuntimeError("Only one or two populations are supported, but the following were found in the data: %r"
+                               % pops)
+        self.populations = tuple(pops)
+        cs = [D.recode_nonseg(c, args.nonseg_cutoff) for c in cs]
+        for c in cs:
+            c.data = D.compress_repeated_obs(c.data)
+        cs = [p for c in cs for p in D.break_long_spans(c, 100000)]
+        cs = D.drop_small_contigs(cs, 100000)
+        self._watterson = D.watterson_theta(cs)
+        self._mutation_counts = Analysis._count_mutations(cs, int(2e-3 * self._N0 / self._rho))
+        self._contigs = cs
+        # ---- split.py:29-36 ----
+        if not any(c.npop == 2 for c in cs):
+            raise RuntimeError("Data contains no joint frequency spectrum information. Split estimation is impossible.")
+        # ---- split.py:51-62 ----
+        self._theta = d1["theta"]
+        self._rho = d1["rho"]
+        if d2["theta"] != self._theta:
+            raise RuntimeError("the marginal fits have different theta: %r, %r" % (self._theta, d2["theta"]))
+        if d2["model"]["N0"] != d1["model"]["N0"]:
+            raise RuntimeError("the marginal fits have different N0: %r, %r" % (d1["model"]["N0"], d2["model"]["N0"]))
+        self.hidden_states = {k: np.array(v, dtype=float) for k, v in d1["hidden_states"].items()}
+        self.hidden_states.update({k: np.array(v, dtype=float) for k, v in d2["hidden_states"].items()})
+        m1, m2 = SMCModel.from_dict(d1["model"]), SMCModel.from_dict(d2["model"])
+        if set(self.populations) != {m1.pid, m2.pid}:
+            raise RuntimeError("the data's populations %r are not those of the marginal fits (%r, %r)"
+                               % (self.populations, m1.pid, m2.pid))
+        self._max_split = float(m2.knots[-1])              # defaults.additional_knots == []
+        self._model = SMCTwoPopulationModel(m1, m2, self._max_split * 0.5)
+        self._init_inference_managers()
+
+    def _init_inference_managers(self):
+        """base.py:89-121: one manager per population tuple, every one with the hidden states [0, inf]."""
+        groups = {}
+        for c in self._contigs:
+            groups.setdefault(tuple(c.pid), []).append(c)
+        for pid, cl in groups.items():
+            a = {tuple(c.a) for c in cl}
+            if len(a) != 1:
+                raise RuntimeError("the contigs of population pair %r have different distinguished lineages: %r"
+                                   % (pid, sorted(a)))
+        hs = np.array([0.0, np.inf])
+        self._ims = {}
+        for pid, cl in groups.items():
+            n = np.max([c.n for c in cl], axis=0)
+            obs = [np.ascontiguousarray(c.data, dtype=np.int32) for c in cl]
+            if len(pid) == 1:
+                im = _smcpp.PyOnePopInferenceManager(int(n[0]), obs, hs, pid, self._pol, device=self._args.device)
+            else:
+                a1, a2 = cl[0].a
+                im = _smcpp.PyTwoPopInferenceManager(int(n[0]), int(n[1]), a1, a2, obs, hs, pid, self._pol,
+                                                     device=self._args.device)
+            im.model = self._model
+            im.theta = self._theta
+            im.rho = self._rho
+            im.alpha = self._alpha = 1
+            self._ims[pid] = im
+
+    # ---- base.py:123-191 ----
+    def run(self, niter=None):
+        for i in range(niter or self._niter):
+            self.E_step()
+            logger.info("Loglik: %f", self.loglik())
+            self.optimize_split()
+            self._scale_step()
+        if self._args.outdir:
+            self.dump(os.path.join(self._args.outdir, "{}.final".format(self._args.base)))
+
+    def optimize_split(self, bounds=None):
+        """`ParameterOptimizer("split", (0, max_split), "model")` on the current E-step statistics."""
+        m = self._model
+
+        def f(x):
+            m.split = x
+            return -float(self.Q())
+
+        res = scipy.optimize.minimize_scalar(f, method="bounded", bounds=bounds or (0.0, self._max_split))
+        logger.info("New split: %g", res.x)
+        m.split = res.x
+        return res
+
+    def _scale_step(self):
+        """`ScaleOptimizer` (plugins/scale_optimizer.py) on the two-population model: one common shift of every coordinate."""
+        m = self._model
+        x0 = np.array(m[:], dtype=float)
+
+        def f(alpha):
+            m[:] = x0 + alpha
+            return -float(self.Q())
+
+        res = scipy.optimize.minimize_scalar(f, method="bounded", bounds=(-1, 1))
+        m[:] = x0 + res.x
+        return res
+
+    def Q(self):
+        q = float(np.sum([self._ims[p].Q(separate=True) for p in self._ims]))
+        return q - self._penalty * self._model.regularizer()
+
+    def E_step(self):
+        for p in self._ims:
+            self._ims[p].E_step()
+
+    def loglik(self, reg=True):
+        ll = sum(im.loglik() for im in self._ims.values())
+        return ll - self._penalty * self._model.regularizer() if reg else ll
+
+    @property
+    def model(self):
+        return self._model
+
+    @property
+    def max_split(self):
+        return self._max_split
+
+    @property
+    def inference_managers(self):
+        return self._ims
+
+    @property
+    def alpha(self):
+        return self._alpha
+
+    @property
+    def rho(self):
+        return self._rho
+
+    @property
+    def contigs(self):
+        return self._contigs
+
+    def dump(self, filename):
+        """`model.final.json` (base.py:186-191); `hidden_states` are those of the two marginal fits, as the reference writes."""
+        write_final_json(filename, self._theta, self._rho, self._alpha, self._model, self.hidden_states)
 
 def write_final_json(filename, theta, rho, alpha, model, hidden_states):
     """`BaseAnalysis.dump` (smcpp/analysis/base.py:186-191): theta / rho / alpha, `model.to_dict()` and the hidden states per
