@@ -283,6 +283,9 @@ def test_unbinned_rows_gamma_from_eigen_power_pieces(engine_opt, M, rows, nconti
         print(f"M = {M}, contig {c}: {len(obs)} un-binned rows ({int(obs[:, 0].sum())} positions): per-row gamma worst column {err.max():.2e} of its "
               f"span (eigensystem kernel: {err0.max():.2e}; the two routes: {(np.max(np.abs(g0 - gam), axis=0) / spans).max():.2e})")
         assert err.max() <= 2e-5
+        assert err0.max() <= 2e-5           # (the eigensystem kernel k_gamma_rows_eig: its columns' sums and decode below)
+        np.testing.assert_allclose(g0.sum(axis=0)[1:], spans[1:], rtol=1e-9)
+        assert np.array_equal(np.asarray(im0.gamma_argmax(c)), g0.argmax(axis=0))
     ll = im.loglik()
     assert abs(ll - sum(lls)) <= LL_TOL * abs(sum(lls)), (ll, lls)
 

@@ -30,6 +30,74 @@ def make_im(g, **kw):
     return im
 
 
+GAMMA_TOL = 2e-5          # per entry of a per-row posterior, times the row's span
+GAMMA_LARGE_TOL = 1e-4    # relative, on the entries that hold 1e-3 of their column's mass or more
+GAMMA_SUM_RTOL = 1e-9     # a column sums to its row's span (hmm.cpp:113-121 normalises to it)
+GAMMA_MARGIN = 1e-5       # decoded index identical where top-1 minus top-2 exceeds this times the span
+
+_ORACLE = {}              # (parameters, contig, save_gamma) -> the restatement's E-step, shared by every test of the process
+
+
+def oracle_estep(pi, T, keys, E, obs, save_gamma=True):
+    """oracle.estep, run once per (parameters, contig) in a process: cases that share a setup reuse it."""
+    import hashlib
+    from oracle import oracle
+    h = hashlib.sha1(b"gamma" if save_gamma else b"")
+    for x in (pi, T, keys, E, obs):
+        x = np.ascontiguousarray(x)
+        h.update(str((x.dtype, x.shape)).encode())
+        h.update(x.tobytes())
+    key = h.hexdigest()
+    if key not in _ORACLE:
+        _ORACLE[key] = oracle.estep(pi, T, keys, E, obs, save_gamma=save_gamma)
+    return _ORACLE[key]
+
+
+def check_gamma_columns(gam, ref, obs, arg_dev=None, label=""):
+    """Every column of a per-row posterior matrix `gam` ([M, L + 1], column l >= 1 the row of span s_l) against the restatement's
+    `ref`, each at the scale of its own row's span:
+      * max_i |gam - ref| <= 2e-5 s_l (column 0, alpha_0 o beta_0, which is not normalised: 2e-5 of its largest entry);
+      * the column sums to s_l to 1e-9 relative;
+      * entries with ref >= 1e-3 s_l to 1e-4 relative;
+      * the decoded index equals the reference's wherever its top-1 / top-2 gap exceeds 1e-5 s_l, and `arg_dev` (the device's
+        decode, when given) equals gam.argmax(0) on every column.
+    Returns the worst value of each measure (printed with `label`)."""
+    obs = np.asarray(obs)
+    M, ncol = ref.shape
+    assert gam.shape == ref.shape == (M, len(obs) + 1), (gam.shape, ref.shape, len(obs))
+    assert np.all(np.isfinite(gam)), f"{label}: {int(np.sum(~np.isfinite(gam)))} non-finite entries"
+    spans = np.concatenate([[1.0], obs[:, 0].astype(float)])
+    d = np.abs(gam - ref)
+    c0 = float(d[:, 0].max() / max(np.abs(ref[:, 0]).max(), 1e-300))
+    assert c0 <= GAMMA_TOL, (label, c0)
+    scale = d[:, 1:].max(axis=0) / spans[1:]
+    sums = np.abs(gam[:, 1:].sum(axis=0) - spans[1:]) / spans[1:]
+    large = ref[:, 1:] >= 1e-3 * spans[1:]
+    rel = np.where(large, d[:, 1:] / np.where(large, ref[:, 1:], 1.0), 0.0)
+    worst = {"scale": float(scale.max(initial=0.0)), "sum": float(sums.max(initial=0.0)), "large": float(rel.max(initial=0.0)),
+             "col0": c0}
+    print(f"{label}: {ncol - 1} rows, worst column of its span {worst['scale']:.2e}, column sum vs span {worst['sum']:.2e}, "
+          f"large entries rel {worst['large']:.2e}, column 0 {c0:.2e}")
+    bad = np.nonzero(scale > GAMMA_TOL)[0]
+    assert len(bad) == 0, f"{label}: {len(bad)} columns off by more than {GAMMA_TOL} of their span, e.g. rows {bad[:8] + 1} " \
+                          f"(spans {spans[1:][bad[:8]]}, errors {scale[bad[:8]]})"
+    bad = np.nonzero(sums > GAMMA_SUM_RTOL)[0]
+    assert len(bad) == 0, f"{label}: {len(bad)} columns do not sum to their span, e.g. rows {bad[:8] + 1} (spans {spans[1:][bad[:8]]}, " \
+                          f"sums {gam[:, 1:].sum(axis=0)[bad[:8]]})"
+    assert worst["large"] <= GAMMA_LARGE_TOL, (label, worst["large"])
+    arg = gam.argmax(axis=0)
+    if M > 1:
+        top2 = np.sort(ref, axis=0)[-2:]
+        strong = (top2[1] - top2[0]) > GAMMA_MARGIN * np.concatenate([[max(np.abs(ref[:, 0]).max(), 1e-300)], spans[1:]])
+        mism = np.nonzero(strong & (arg != ref.argmax(axis=0)))[0]
+        assert len(mism) == 0, f"{label}: decoded index differs on columns {mism[:10]}"
+    if arg_dev is not None:
+        arg_dev = np.asarray(arg_dev)
+        assert arg_dev.shape == arg.shape and np.array_equal(arg_dev, arg), \
+            f"{label}: device decode differs from argmax of its own gamma on columns {np.nonzero(arg_dev != arg)[0][:10]}"
+    return worst
+
+
 def check_against(g, im, save_gamma):
     ll = im.loglik()
     assert abs(ll - float(g["loglik"])) <= LL_TOL * abs(float(g["loglik"])), (ll, float(g["loglik"]))
@@ -53,6 +121,13 @@ def check_against(g, im, save_gamma):
     st = int(g["gamma_stride"])
     sub = gam[:, ::st]
     assert np.max(np.abs(sub - g["gamma_sub"])) <= 2e-5 * max(1.0, float(np.abs(g["gamma_sub"]).max()))
+    # the compiled reference's strided columns, each at the scale of its own row's span (column 0: of its largest entry)
+    sub_spans = np.concatenate([[max(float(np.abs(g["gamma_sub"][:, 0]).max()), 1e-300)], g["obs"][:, 0].astype(float)])[::st]
+    sub_err = np.max(np.abs(sub - g["gamma_sub"]), axis=0) / sub_spans
+    assert sub_err.max() <= GAMMA_TOL, f"strided columns {np.nonzero(sub_err > GAMMA_TOL)[0][:10] * st} off their span's scale"
+    # every column against the C restatement run on the golden's own parameters
+    o = oracle_estep(g["pi"], g["T"], g["keys"], g["E"], g["obs"])
+    check_gamma_columns(gam, o["gamma"], g["obs"], arg_dev=im.gamma_argmax(0), label=str(g.get("name", "golden")))
     arg = gam.argmax(axis=0)
     strong = g["gamma_margin"] > 1e-5
     mism = np.nonzero(arg != g["gamma_argmax"])[0]
@@ -414,8 +489,9 @@ def test_state_count_sweep_vs_oracle(engine_opt, M, n, length, chunk):
         g_ref = o["gamma"]
         assert gams[c].shape == g_ref.shape
         assert np.max(np.abs(gams[c] - g_ref)) <= 2e-5 * max(1.0, float(np.abs(g_ref).max()))
-        top2 = np.sort(g_ref, axis=0)[-2:] if M > 1 else None
+        check_gamma_columns(gams[c], g_ref, ob, arg_dev=im.gamma_argmax(c), label=f"M = {M}, contig {c}")
         if M > 1:
+            top2 = np.sort(g_ref, axis=0)[-2:]
             margin = (top2[1] - top2[0]) / np.maximum(top2[1], 1e-300)
             mism = np.nonzero(gams[c].argmax(axis=0) != g_ref.argmax(axis=0))[0]
             assert not np.any(margin[mism] > 1e-5)

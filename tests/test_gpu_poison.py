@@ -23,7 +23,7 @@ import pytest
 
 from conftest import GOLDEN, load_golden, rel_err
 from test_gpu_argmax import _check_stats, _load as _load_headline, _manager as _headline_manager, argmax_report
-from test_gpu_parity import LL_TOL, STAT_TOL, check_against, make_im
+from test_gpu_parity import LL_TOL, STAT_TOL, check_against, check_gamma_columns, make_im
 
 pytestmark = pytest.mark.gpu
 
@@ -121,6 +121,7 @@ def _oracle_check(contigs, every=1, stat_tol=STAT_TOL, gamma=False, xs_entry_tol
                     top2 = np.sort(o["gamma"], axis=0)[-2:]
                     strong = (top2[1] - top2[0]) > 1e-5 * spans
                     assert not np.any(strong & (gams[c].argmax(axis=0) != o["gamma"].argmax(axis=0))), c
+                check_gamma_columns(gams[c], o["gamma"], ob, arg_dev=im.gamma_argmax(c), label=f"contig {c}")
     return check
 
 
@@ -151,6 +152,7 @@ CASES += ["gammaeig:G4_M64_n20_2Mbp", "gammaeig:G5_M48_twopop_layout",        # 
           "twopop:2:0", "twopop:1:1", "m1",
           "sweep:33", "sweep:130",                                             # padding columns with save_gamma (G2 above: M = 51)
           "cut:144", "cut:300", "pieces:128:1", "pieces:96:2",
+          "pieces:150:2", "pieces:130:2:eig",                                  # three states per lane; k_span_q + k_gamma_rows_eig
           "bigm:512:0", "bigm:768:0", "bigm:768:1", "bigm:1024:0",
           "tiny", "headline:0", "headline:1"]
 
@@ -255,17 +257,20 @@ def _case(case, engine_opt):
         return build, _oracle_check(obs, gamma=True, xs_entry_tol=5e-5), True, False
     if kind == "pieces":
         # test_unbinned_rows_gamma_from_eigen_power_pieces: un-binned rows, per-row gammas from eigen-power pieces (k_piece_vectors)
-        M, nc = int(arg[0]), int(arg[1])
+        # ("eig": SMCPP_GAMMA_PIECES=0, the eigensystem kernel of M > 64 on the same rows)
+        M, nc, eig = int(arg[0]), int(arg[1]), arg[2:] == ["eig"]
         rows = 400 if M == 128 else 300
         contigs = [np.ascontiguousarray(synth.synth_posterior_contig(rows - 40 * c, 8, seed=11 + c), dtype=np.int32) for c in range(nc)]
         engine_opt("SMCPP_SPLIT_SPANS", "0")
+        if eig:
+            engine_opt("SMCPP_GAMMA_PIECES", "0")
 
         def build():
             im = _model_manager(8, contigs, M=M, theta=2e-4, rho=6e-5)
             return im
 
         def check(im):
-            assert im.describe()["plan"]["per_row_gamma"] == "eigen-power pieces + scan steps"
+            assert im.describe()["plan"]["per_row_gamma"] == ("eigensystem" if eig else "eigen-power pieces + scan steps")
             _oracle_check(contigs, gamma=True)(im)
         return build, check, True, False
     if kind == "bigm":
