@@ -25,7 +25,15 @@ _lib = None
 def build(force: bool = False) -> str:
     src = os.path.join(_HERE, "hmm_oracle.c")
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
-        subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-fopenmp", "-o", _LIB_PATH, src, "-lm"])
+        # compiled under a name of this process's own, then renamed into place: processes that find the library stale at the
+        # same time (the ranks of tests/test_dist.py) never load a half-written one
+        tmp = os.path.join(_HERE, f".liboracle.{os.getpid()}.so")
+        try:
+            subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-fopenmp", "-o", tmp, src, "-lm"])
+            os.replace(tmp, _LIB_PATH)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
     return _LIB_PATH
 
 

@@ -1,5 +1,27 @@
 // engine_manager.hpp - part of the ONE translation unit engine.hip (included there, in order; not a standalone header):
 // the manager (struct smcpp_im): observation layout, chunks, slabs, device allocation.
+
+// How the statistics phase of an E-step is arranged: the stream of every branch and the form of every kernel family, resolved from the
+// manager's shape and the switches (smcpp_im::resolve_stats_plan).  The launches only read it; smcpp_describe() reports the last one.
+struct StatsPlan {
+    enum Stream { MAIN, SECOND, THIRD, HIGH };          // stream, stream2, stream3, stream_hi
+    enum Rank { RANK_PER_SLAB, RANK_TEAMS, RANK_WIDE };  // k_rank_acc<.>, k_rank_acc<., true>, k_rank_acc_wide (modes 0 / 2)
+    enum Eigen { EIG_NONE, EIG_FOLD_SCANS, EIG_FOLD_MATRIX_CORES, EIG_GEN2, EIG_CLASSIC };
+    enum Gsum { GSUM_ONE_PASS, GSUM_OWN_STREAM, GSUM_SPAN_GT1_TAIL, GSUM_SPAN1 };   // where the per-key gamma sums are reduced
+    enum Gamma { GAMMA_NONE, GAMMA_SCAN, GAMMA_PIECES, GAMMA_EIG_BATCHES, GAMMA_EIG_ROWS };
+    bool resolved = false, split = false;  // split: the second stream forks off the chains' end and joins before the finalisation
+    Stream span_gt1 = MAIN, span1 = MAIN, gsum = MAIN, loglik = MAIN, gamma = MAIN;
+    bool s1_one_pass = false;              // span-1 rows: k_rank_acc<3> (rank update + gamma sums) instead of k_s1_scalars + k_rank_acc<0>
+    Rank rank = RANK_PER_SLAB;
+    bool teams_span1 = false, teams_one_pass = false, teams_span_gt1 = false;   // per rank update: one partial per team of slabs
+    Eigen eigen = EIG_NONE;
+    bool rank_early = false;               // the span > 1 rank update goes ahead of the span-1 branch
+    Gsum gsum_at = GSUM_SPAN1;
+    Gamma gamma_form = GAMMA_NONE;
+    bool gamma_beside = false;             // the per-row gammas run beside the statistics
+    bool fin_signals = false;              // the finalisation may raise the completion word itself
+};
+
 struct smcpp_im {
     // ---- static problem description -------------------------------------------------------------------------
     int npop = 1, keylen = 3, M = 0, Mp = 0, NPL = 1, NT = 1, n_contigs = 0, K = 0, G = 0, Ke = 0;
@@ -66,11 +88,22 @@ struct smcpp_im {
     bool save_gamma = false, gamma_valid = false, estep_done = false;
     // ---- device -----------------------------------------------------------------------------------------------
     int device = 0;
-    hipStream_t stream3 = nullptr;         // third branch of the statistics (per-key gamma sums)
+    hipStream_t stream3 = nullptr;         // third branch of the statistics (log-likelihood or per-key gamma sums)
     hipStream_t stream = nullptr, stream2 = nullptr;   // stream2: backward chain when it may overlap the forward one
-    hipEvent_t ev[24];                                  // 10..13: forward / backward interval of the eigen-free pre-pass; 14: span-1 scalars done
+    hipStream_t stream_hi = nullptr;       // per-row gammas beside the statistics
+    // Event slots: every record and wait names what it orders
+    enum Ev {
+        EV_ESTEP, EV_FIRST_PASS,           // E-step start; in front of the first chain launch (eigen-free pre-pass or scan chains)
+        EV_PRE_FWD_END, EV_PRE_BWD_START, EV_PRE_BWD_END,           // eigen-free pre-pass: the forward and backward chains' intervals
+        EV_CHAINS_START, EV_BWD_START, EV_FWD_END, EV_CHAIN_SYNC,   // dense chains: intervals, hand-over between their two streams
+        EV_CHAINS_END, EV_STATS_FORK,      // behind the last pass (the statistics' fork on the scan chains); fork on the dense ones
+        EV_ARENA,                          // the parameter arena copied on the second stream has landed
+        EV_LOGLIK_DONE, EV_RANK2_DONE, EV_S1_SCALARS, EV_GSUM_FORK, EV_GSUM_DONE, EV_SPAN1_DONE, EV_SIDE_DONE,   // statistics branches
+        EV_GAMMA_FORK, EV_GAMMA_DONE,      // per-row gammas beside the statistics
+        EV_STATS_DONE, EV_COUNT            // end of the E-step's queue
+    };
+    hipEvent_t ev[EV_COUNT];
     int dual_stream = 1;
-    hipStream_t stream_hi = nullptr;
     bool chains_dual = false;
     DevBuf<RowInfo> d_rowinfo;
     DevBuf<int2> d_rowdesc;
@@ -143,7 +176,7 @@ struct smcpp_im {
     // vector the PREVIOUS converged E-step left (parity ss_warm_parity of the end-vector arrays) instead of pi / the uniform
     // vector, and one light pass fewer runs; pass indices then start at ss_pass0 (1 or 2: the parity the first pass reads)
     bool ss_warm_valid = false;
-    // lean E-steps copy the (small) parameter arena on stream2 while the chains run; the statistics wait for ev[20]
+    // lean E-steps copy the (small) parameter arena on stream2 while the chains run; the statistics wait for EV_ARENA
     bool arena_side = false;
     int ss_warm_parity = 0, ss_pass0 = 0;
     std::vector<int> ss_slot_of_key;       // frequency rank of every key (slot 0 = most rows)
@@ -161,7 +194,7 @@ struct smcpp_im {
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;
     std::vector<int> gp_pfirst;
-    bool gp_built = false, gamma_pieces_last = false;
+    bool gp_built = false;
     DevBuf<GPiece> d_gp_pieces;
     DevBuf<GTile> d_gp_tiles;
     DevBuf<int> d_gp_pfirst;
@@ -236,8 +269,6 @@ struct smcpp_im {
     int done_epoch = 0;
     DevBuf<unsigned> d_fin_ctr;          // blocks of the finalisation launches that raise h_done themselves (k_fin_both)
     unsigned fin_target = 0;
-    int fold_done_epoch = 0;             // != 0: the statistics being enqueued end the queue and signal this epoch
-    bool done_folded = false;
     bool timing_pending = false;         // the event intervals of the last E-step are read when somebody asks (resolve_timing)
     double t_host01 = 0, t_host12 = 0;
     void resolve_timing();
@@ -297,9 +328,24 @@ struct smcpp_im {
     ChainArgs chain_args();
     void run_chains();
     void run_stats();            // = enqueue_stats() unless run_chains() already queued them, + finish_stats()
-    void enqueue_stats();
+    // signal_epoch != 0: nothing follows on the main stream, and the statistics may raise the completion word with this epoch
+    // themselves; returns whether they do
+    bool enqueue_stats(int signal_epoch = 0);
     void finish_stats();
     bool stats_enqueued = false;
+    StatsPlan stats_plan;        // of the last enqueue_stats()
+    StatsPlan resolve_stats_plan();
+    // (enqueue_stats' helpers and branch launchers)
+    hipStream_t plan_stream(StatsPlan::Stream x) const {
+        return x == StatsPlan::SECOND ? stream2 : x == StatsPlan::THIRD ? stream3 : x == StatsPlan::HIGH ? stream_hi : stream;
+    }
+    // what is queued on `from` so far precedes what is queued on `to` from now on
+    void hand_over(Ev e, hipStream_t from, hipStream_t to) { HIPCHK(hipEventRecord(ev[e], from)); HIPCHK(hipStreamWaitEvent(to, ev[e], 0)); }
+    void fork_from_chains(hipStream_t x);
+    S1Args s1_args(bool span_gt1);
+    AccArgs acc_args(const std::vector<Slab> &sl, const Slab *d_sl, const int *perm, const int2 *permk, double *part, double *gpart);
+    void launch_span_gt1_rank(const StatsPlan &p), launch_span1_branch(const StatsPlan &p), launch_gamma_rows(const StatsPlan &p);
+    void launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa);
     void estep();
     void fetch_stats();
     void prepare_params();
@@ -471,8 +517,7 @@ void smcpp_im::build(int npop_, const int *nn, const int *nna, int n_contigs_, c
     HIPCHK(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&stream3, hipStreamNonBlocking));
     {
-        // the eigen-free statistics end in a serial fold on a few CUs: its branch gets a stream of the highest priority so that its
-        // workgroups are placed ahead of the chip-filling rank updates they run beside
+        // (the per-row gammas beside the statistics: the highest priority places their workgroups ahead of the rank updates)
         int least = 0, greatest = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
         HIPCHK(hipStreamCreateWithPriority(&stream_hi, hipStreamNonBlocking, greatest));

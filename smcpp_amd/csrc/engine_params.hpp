@@ -575,14 +575,14 @@ void smcpp_im::host_prep_and_upload() {
     }
     if (off > need) throw std::runtime_error("internal: parameter arena overflow");
     auto tp2 = std::chrono::steady_clock::now();
-    arena_side = lean && stream2 != nullptr && dual_stream;
+    arena_side = lean && dual_stream;
     // SMCPP_DEBUG_POISON=nan: the whole arena is NaN again in front of its copy, on the copy's stream - a consumer that waits for the
     // copy sees this E-step's parameters, one that races it NaN instead of the previous E-step's plausible ones
     if (opt().poison_nan) HIPCHK(hipMemsetAsync(d_param, 0xff, param_cap, arena_side ? stream2 : s));
     if (arena_side) {
         // nothing the chains read lives in this arena: the copy runs beside them, the statistics wait for it
         HIPCHK(hipMemcpyAsync(d_param, hb, off, hipMemcpyHostToDevice, stream2));
-        HIPCHK(hipEventRecord(ev[20], stream2));
+        HIPCHK(hipEventRecord(ev[EV_ARENA], stream2));
     } else
     HIPCHK(hipMemcpyAsync(d_param, hb, off, hipMemcpyHostToDevice, s));
     // (d_r / scale)^span for every (span, eigen key) group: G x M calls of pow() - 2 ms of host time on data with a few

@@ -3,28 +3,31 @@
 // ---------------------------------------------------------------------------------------------------------------
 // kernel launches
 // ---------------------------------------------------------------------------------------------------------------
+// Raise a kernel's dynamic LDS limit to 160 KiB, once per kernel (the attribute holds for the process)
+template <auto KERNEL>
+static void lds_limit_once() {
+    static bool once = false;
+    if (!once) { HIPCHK(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; }
+}
+
 // the cooperative chains (chains2.hpp): pass 0 and the re-run passes are separate instantiations
 template <int MT_, bool TAB_, bool RERUN_, bool HOT2_>
 static void launch_chain_coop2_tt(bool fwd, const ChainArgs &a, const CoopArgs &ca, size_t shm, hipStream_t s) {
     if (fwd) {
-        static bool once = false;
-        if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_fwd_coop2<MT_, TAB_, RERUN_, HOT2_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; }
+        lds_limit_once<k_fwd_coop2<MT_, TAB_, RERUN_, HOT2_>>();
         hipLaunchKernelGGL((k_fwd_coop2<MT_, TAB_, RERUN_, HOT2_>), dim3(a.nchunks), dim3(MT_ * 4), shm, s, a, ca);
     } else {
-        static bool once = false;
-        if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_bwd_coop2<MT_, TAB_, RERUN_, HOT2_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; }
+        lds_limit_once<k_bwd_coop2<MT_, TAB_, RERUN_, HOT2_>>();
         hipLaunchKernelGGL((k_bwd_coop2<MT_, TAB_, RERUN_, HOT2_>), dim3(a.nchunks), dim3(MT_ * 4), shm, s, a, ca);
     }
 }
 template <int MT_, bool TAB_>
 static void launch_chain_power_t(bool fwd, const ChainArgs &a, const CoopArgs &ca, size_t shm, hipStream_t s) {
     if (fwd) {
-        static bool once = false;
-        if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_fwd_coop2<MT_, TAB_, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; }
+        lds_limit_once<k_fwd_coop2<MT_, TAB_, false, false, true>>();
         hipLaunchKernelGGL((k_fwd_coop2<MT_, TAB_, false, false, true>), dim3(a.nchunks), dim3(MT_ * 4), shm, s, a, ca);
     } else {
-        static bool once = false;
-        if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_bwd_coop2<MT_, TAB_, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; }
+        lds_limit_once<k_bwd_coop2<MT_, TAB_, false, false, true>>();
         hipLaunchKernelGGL((k_bwd_coop2<MT_, TAB_, false, false, true>), dim3(a.nchunks), dim3(MT_ * 4), shm, s, a, ca);
     }
 }
@@ -89,30 +92,19 @@ static bool launch_chain_big(bool fwd, int Mp, const ChainArgs &a, const BigArgs
     }
 }
 
-template <int NT_>
-static void launch_uw_t(const UWArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL(k_eig_uw<NT_>, dim3(a.nslabs), dim3(64), 0, s, a);
-}
 static void launch_uw(int nt, const UWArgs &a, hipStream_t s) {
     switch (nt) {
-#define C_(x) case x: launch_uw_t<x>(a, s); break;
+#define C_(x) case x: hipLaunchKernelGGL(k_eig_uw<x>, dim3(a.nslabs), dim3(64), 0, s, a); break;
         C_(1) C_(2) C_(3) C_(4) C_(5) C_(6) C_(7) C_(8) C_(9) C_(10) C_(11) C_(12) C_(13) C_(14) C_(15) C_(16)
 #undef C_
         default: throw std::runtime_error("unsupported number of hidden states");
     }
 }
-template <int NPL_>
-static void launch_s1_t(const S1Args &a, hipStream_t s) {
-    hipLaunchKernelGGL(k_s1_scalars<NPL_>, dim3(a.nslabs), dim3(256), 0, s, a);
-}
 static void launch_s1(int npl, const S1Args &a, hipStream_t s) {
     switch (npl) {
-        case 1: launch_s1_t<1>(a, s); break;
-        case 2: launch_s1_t<2>(a, s); break;
-        case 3: launch_s1_t<3>(a, s); break;
-        case 4: launch_s1_t<4>(a, s); break;
-        case 8: launch_s1_t<8>(a, s); break;
-        case 16: launch_s1_t<16>(a, s); break;
+#define C_(x) case x: hipLaunchKernelGGL(k_s1_scalars<x>, dim3(a.nslabs), dim3(256), 0, s, a); break;
+        C_(1) C_(2) C_(3) C_(4) C_(8) C_(16)
+#undef C_
         default: throw std::runtime_error("unsupported number of hidden states");
     }
 }
@@ -211,17 +203,17 @@ void smcpp_im::stage_static_and_prepass() {
         pre_bargs.qBf = d_qBf.p; pre_bargs.qBb = d_qBb.p;
         a.variant = 1; a.pass = 0;
         if (sb != s) {
-            HIPCHK(hipEventRecord(ev[6], s));
-            HIPCHK(hipStreamWaitEvent(sb, ev[6], 0));
+            HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], s));
+            HIPCHK(hipStreamWaitEvent(sb, ev[EV_CHAIN_SYNC], 0));
         }
-        HIPCHK(hipEventRecord(ev[10], s));
+        HIPCHK(hipEventRecord(ev[EV_FIRST_PASS], s));
         a.changed = d_changed_f.p;
         launch_chain_big(true, Mp, a, pre_bargs, s);
-        HIPCHK(hipEventRecord(ev[11], s));
-        HIPCHK(hipEventRecord(ev[12], sb));
+        HIPCHK(hipEventRecord(ev[EV_PRE_FWD_END], s));
+        HIPCHK(hipEventRecord(ev[EV_PRE_BWD_START], sb));
         a.changed = d_changed_b.p;
         launch_chain_big(false, Mp, a, pre_bargs, sb);
-        HIPCHK(hipEventRecord(ev[13], sb));
+        HIPCHK(hipEventRecord(ev[EV_PRE_BWD_END], sb));
         HIPCHK(hipGetLastError());
         prepass_launched = true;
         return;
@@ -255,17 +247,17 @@ void smcpp_im::stage_static_and_prepass() {
     a.variant = 1; a.pass = 0;
     if (!(opt().i(smcpp_opt::O_BWD_PRIO_MASK, 7) & 1)) a.prio = 0;
     if (sb != s) {
-        HIPCHK(hipEventRecord(ev[6], s));
-        HIPCHK(hipStreamWaitEvent(sb, ev[6], 0));
+        HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], s));
+        HIPCHK(hipStreamWaitEvent(sb, ev[EV_CHAIN_SYNC], 0));
     }
-    HIPCHK(hipEventRecord(ev[10], s));
+    HIPCHK(hipEventRecord(ev[EV_FIRST_PASS], s));
     a.changed = d_changed_f.p;
     launch_chain_coop(true, Mp, a, cargs, tab_c, shm_c, s);
-    HIPCHK(hipEventRecord(ev[11], s));
-    HIPCHK(hipEventRecord(ev[12], sb));
+    HIPCHK(hipEventRecord(ev[EV_PRE_FWD_END], s));
+    HIPCHK(hipEventRecord(ev[EV_PRE_BWD_START], sb));
     a.changed = d_changed_b.p;
     launch_chain_coop(false, Mp, a, cargs, tab_c, shm_c, sb);
-    HIPCHK(hipEventRecord(ev[13], sb));
+    HIPCHK(hipEventRecord(ev[EV_PRE_BWD_END], sb));
     HIPCHK(hipGetLastError());
     if (dbg_level == 2) { HIPCHK(hipStreamSynchronize(s)); HIPCHK(hipStreamSynchronize(sb)); fprintf(stderr, "[power] pre-pass ok\n"); }
     prepass_launched = true;
@@ -324,10 +316,10 @@ void smcpp_im::run_chains() {
     const bool dual = dual_stream && ((chain_mode == 2 && Mp <= 64) || chain_mode == 4 || Mp > 64);
     hipStream_t sb = dual ? stream2 : s;
     if (dual) {
-        HIPCHK(hipEventRecord(ev[6], s));              // parameters / zeroed flags are ready on the main stream
-        HIPCHK(hipStreamWaitEvent(sb, ev[6], 0));
+        HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], s));              // parameters / zeroed flags are ready on the main stream
+        HIPCHK(hipStreamWaitEvent(sb, ev[EV_CHAIN_SYNC], 0));
     }
-    HIPCHK(hipEventRecord(ev[1], s));
+    HIPCHK(hipEventRecord(ev[EV_CHAINS_START], s));
     bool fdone = false, bdone = false;
     int fq = -1, bq = -1;
     bool first_round = true;
@@ -342,7 +334,7 @@ void smcpp_im::run_chains() {
                     throw std::runtime_error("internal: no dense chain kernel for this number of hidden states");
             }
         }
-        if (first_round) HIPCHK(hipEventRecord(ev[2], dual ? sb : s));
+        if (first_round) HIPCHK(hipEventRecord(ev[EV_BWD_START], dual ? sb : s));
         if (!bdone) {
             a.changed = d_changed_b.p;
             for (; launched_b < want_b; ++launched_b) {
@@ -354,14 +346,14 @@ void smcpp_im::run_chains() {
             }
         }
         HIPCHK(hipGetLastError());
-        if (first_round && dual) HIPCHK(hipEventRecord(ev[7], s));      // end of the first batch of forward passes
+        if (first_round && dual) HIPCHK(hipEventRecord(ev[EV_FWD_END], s));      // end of the first batch of forward passes
         HIPCHK(hipMemcpyAsync(chf, d_changed_f.p, sizeof(int) * (max_pass + 1), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(chb, d_changed_b.p, sizeof(int) * (max_pass + 1), hipMemcpyDeviceToHost, sb));
         if (dual) {
-            HIPCHK(hipEventRecord(ev[6], sb));
-            HIPCHK(hipStreamWaitEvent(s, ev[6], 0));   // the statistics (main stream) need both chains
+            HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], sb));
+            HIPCHK(hipStreamWaitEvent(s, ev[EV_CHAIN_SYNC], 0));   // the statistics (main stream) need both chains
         }
-        HIPCHK(hipEventRecord(ev[3], s));
+        HIPCHK(hipEventRecord(ev[EV_CHAINS_END], s));
         // Optimistic: the first batch normally contains the quiet pass (it is sized from the previous E-step), so the
         // statistics are queued behind it BEFORE the host waits for the flags - the read-back round trip and their launch
         // latency disappear behind GPU work.  If the flags say otherwise the statistics are simply queued again later.
@@ -516,11 +508,7 @@ bool smcpp_im::ss_extract_generators() {
 
 template <int NPL_, bool HYB_, bool ALL_, bool H32_ = false>
 static void launch_chain_ss_tt(const SsArgs &a, int ntasks, size_t shm, hipStream_t s, int wgw) {
-    static bool once = false;
-    if (!once) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_chain_ss<NPL_, HYB_, ALL_, H32_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        once = true;
-    }
+    lds_limit_once<k_chain_ss<NPL_, HYB_, ALL_, H32_>>();
     hipLaunchKernelGGL((k_chain_ss<NPL_, HYB_, ALL_, H32_>), dim3(ntasks / wgw), dim3(64 * wgw), shm, s, a);
 }
 template <int NPL_, bool HYB_>
@@ -673,7 +661,7 @@ void smcpp_im::ss_launch_initial() {
     a.dbg = nullptr;
     if (opt().has(smcpp_opt::O_DEBUG_CYCLES)) { d_dbg.alloc(16); d_dbg.zero(s); a.dbg = d_dbg.p; }
     HIPCHK(hipMemcpyAsync(d_pre, pre_stage.base, off, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ev[10], s));
+    HIPCHK(hipEventRecord(ev[EV_FIRST_PASS], s));
     ss_launched = ss_pass0;
     // (round 5) the passes launched up front end with the pass that is expected to rewrite no end vector - the all-skip pass behind
     // it (0.01 ms of kernel + its place in the queue) is not launched: run_chains_ss certifies from the end-vector flags
@@ -683,8 +671,8 @@ void smcpp_im::ss_launch_initial() {
     const int want = std::min(max_pass, std::max(ss_pass0 + (last_ss_passes > 0 ? last_ss_passes + (cert_launch || ss_need_cert_pass ? 1 : 0) : 6),
                                                  std::max(ss_light_f, ss_light_b) + 2));
     ss_launch_passes(want);
-    // (no event behind the passes here: run_chains_ss records ev[3] at this very position, and every record costs the queue ~3 us
-    // in front of the statistics' critical branch - tools/sync_lab.hip)
+    // (no event behind the passes here: run_chains_ss records EV_CHAINS_END at this very position, and every record costs the queue
+    // ~3 us in front of the statistics' critical branch - tools/sync_lab.hip)
 }
 
 bool smcpp_im::wait_done(int epoch) {
@@ -719,20 +707,17 @@ void smcpp_im::run_chains_ss() {
     int q = -1, first_launched = -1;      // (first_launched: passes launched when the first round failed to certify, -1: it did)
     const bool poll = !opt().off(smcpp_opt::O_POLL);
     while (true) {
-        HIPCHK(hipEventRecord(ev[3], s));
+        HIPCHK(hipEventRecord(ev[EV_CHAINS_END], s));
         // optimistic, as run_chains(): the statistics are queued right behind the passes; the host only looks at the flags (pinned
         // memory the kernels wrote) when the queue has drained; in the rare round that needs more passes the statistics are redone
-        const bool spec_gamma = !opt().off(smcpp_opt::O_SPEC_GAMMA);
-        done_folded = false;
-        if (first_round && (!save_gamma || spec_gamma)) {              // (save_gamma too: the passes launched up front almost always suffice)
-            fold_done_epoch = poll ? done_epoch + 1 : 0;
-            enqueue_stats();
-            fold_done_epoch = 0;
-        } else stats_enqueued = false;
+        // (save_gamma too: the passes launched up front almost always suffice)
+        bool signalled = false;
+        if (first_round) signalled = enqueue_stats(poll ? done_epoch + 1 : 0);
+        else stats_enqueued = false;
         done_covers_stats = stats_enqueued;
         if (poll) {
             ++done_epoch;
-            if (!done_folded) hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, s, d_done_view, done_epoch);
+            if (!signalled) hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, s, d_done_view, done_epoch);
             if (!wait_done(done_epoch)) throw std::runtime_error("the device did not signal completion");
         } else HIPCHK(hipStreamSynchronize(s));
         first_round = false;
@@ -781,273 +766,177 @@ void smcpp_im::finish_stats() {
     stats_enqueued = false;
 }
 
-void smcpp_im::enqueue_stats() {
-    hipStream_t s = stream;
-    if (h_ll_cap < n_contigs) {
-        if (h_ll) (void)hipHostFree(h_ll);
-        h_ll_cap = n_contigs;
-        HIPCHK(hipHostMalloc((void **)&h_ll, sizeof(double) * h_ll_cap, hipHostMallocCoherent | hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void **)&d_ll_view, h_ll, 0));
+// ---- statistics: one plan per enqueue (resolve_stats_plan), then branch launchers that only read it ----
+// One rank update: k_rank_acc_wide (operand rows staged through LDS; modes 0 / 2), k_rank_acc over teams of up to four slabs of one
+// reduction range that add their accumulators through LDS (teams != nullptr), or k_rank_acc with one wavefront per slab
+template <int MODE>
+static void launch_rank_acc(AccArgs a, bool wide, const int2 *teams, size_t nteams, hipStream_t s) {
+    a.teams = teams;
+    const unsigned nx = teams ? (unsigned)nteams : (unsigned)a.nslabs, ny = MODE == 3 ? 1u : (unsigned)(a.NB * a.NB);
+    if constexpr (MODE == 0 || MODE == 2) {
+        if (wide) {
+            lds_limit_once<k_rank_acc_wide<MODE, 8>>();
+            const dim3 grid(nx, (unsigned)(((a.Mp + 255) / 256) * ((a.Mp + 127) / 128)));
+            hipLaunchKernelGGL((k_rank_acc_wide<MODE, 8>), grid, dim3(512), RW_LDS, s, a);
+            return;
+        }
     }
-    // The parameter arena of a lean E-step (Td, the emission table of a set_raw manager, the groups' log-scales) is copied on the
-    // SECOND stream beside the chains (engine_params.hpp: arena_side, event 20).  The main stream waits for it here; (round 6) so
-    // does EVERY side stream at the point where it forks off the chains' end (`arena_wait` below) - until round 6 only the main
-    // stream waited, behind the fork event, and a side-stream kernel (k_loglik_partial reads the log-scales, the rank updates of a
-    // set_raw manager the emission table) could run before the copy had landed: an order-dependent wrong log-likelihood on recycled
-    // device memory, NaN under SMCPP_DEBUG_POISON at M = 768 on 70 rows (tools/poison_probe.py found it).  A wait in front of the
-    // fork event itself was measured at 12 us per eval (every branch then starts behind the barrier packet); on the side streams,
-    // which have slack, it costs nothing measurable.
-    if (arena_side) HIPCHK(hipStreamWaitEvent(s, ev[20], 0));
-    auto arena_wait = [&](hipStream_t x) { if (arena_side && x != s) HIPCHK(hipStreamWaitEvent(x, ev[20], 0)); };
-    // log-likelihood (also materialises log_c per row)
-    LoglikArgs la;
-    la.cnorm = d_cnorm.p; la.rowinfo = d_rowinfo.p; la.g_logscale = d_g_logscale.p;
-    la.contig_base = d_contig_base.p; la.contig_L = d_contig_L.p; la.partial = d_llpart.p; la.loglik = d_loglik.p;
-    la.logc = d_logc.p; la.nblk = llblk;
-    la.loglik_host = d_ll_view;          // the final kernel writes the per-contig values into the pinned array as well: no copy
-    // save_gamma: the per-row gammas of the span > 1 rows (2 M^3 flop each, the matrix pipe's business for ~1 ms on a million rows)
-    // need alpha, beta and the eigensystems only - not a single statistic: they run on their own stream BESIDE the (memory- and
-    // latency-bound) statistics instead of behind them
-    // (round 6) long rows at 64 < M <= 256 on a transition matrix with the reference's structure: eigen-power pieces + scan steps instead
-    // of the scalar eigensystem kernel (they read the statistics' own U / W products, so they stay behind them on the main stream)
-    const bool gamma_pieces = save_gamma && n_e_rows > 0 && !eigfree && NT > 4 && Mp <= 256 && !opt().off(smcpp_opt::O_GAMMA_PIECES) &&
-                              (double)gamma_piece_count() * Mp * 20.0 < 96e9 && (ss_active || ss_generators_only());
-    const bool gamma_side = save_gamma && n_e_rows > 0 && dual_stream && stream_hi != nullptr && !gamma_pieces &&
-                            !opt().off(smcpp_opt::O_GAMMA_SIDE);
-    if (save_gamma) {
-        d_gamma_rows.alloc((size_t)total_rows * Mp);
-        // Every row 1 .. L of a contig is written whole by the statistics (span-1 rows: k_s1_scalars; span > 1 rows: the per-row gamma
-        // kernels); only row 0 (column 0 of the caller's matrix comes from gamma0) is nobody's: it alone is cleared.  Until round 6 the
-        // WHOLE buffer was cleared here, on the main stream - behind the scan chains' fork event (ev[3], recorded by run_chains_ss), so
-        // the span-1 branch on its side stream could write rows the memset then wiped: zero columns in the decoded path on a timing-
-        // dependent 2 - 7 % of the headline contig (tests/test_gpu_argmax.py, seen once the suite's order shifted the timing).
-        for (int c = 0; c < n_contigs; ++c)
-            HIPCHK(hipMemsetAsync(d_gamma_rows.p + (size_t)contig_base[c] * Mp, 0, sizeof(double) * Mp, s));
-        if (gamma_side) { HIPCHK(hipEventRecord(ev[22], s)); HIPCHK(hipStreamWaitEvent(stream_hi, ev[22], 0)); }
+    if constexpr (MODE != 1) {
+        if (teams) { hipLaunchKernelGGL((k_rank_acc<MODE, true>), dim3(nx, ny), dim3(256), 0, s, a); return; }
     }
-    // The eigen-row branch (U/W products, rank update, span-Q Hadamard, Y) does not depend on the span-1 branch
-    // (log_c, omega_1, rank update); with two streams the short launches of one fill the gaps of the other.
-    const bool split_streams = dual_stream && stream2 != nullptr && !slabs_eg.empty();
-    const int stats_variant = opt().i(smcpp_opt::O_STATS_VARIANT, 0);
-    // Eigen-free statistics of small inputs: the branch rank update of the span > 1 rows -> reduction -> span fold (2 x s_max serial
-    // steps) is the critical path of the phase, and a hop between two streams costs ~10 us on this runtime (tools/sync_lab.hip:
-    // event record -> wait on another queue; 2 us between two kernels of one queue).  So THAT branch stays on the main stream,
-    // directly behind the last pass of the chains and in front of the finalisation, and the two span-1 branches (which have slack)
-    // fork to the side streams.  (Rounds 2-3 had it the other way round: 40 us between the chains' end and the first kernel of the
-    // critical branch.)  SMCPP_STATS_VARIANT & 4 restores the old arrangement.
-    const bool crit_main = eigfree && dual_stream && stream2 != nullptr && !slabs_eg.empty() && !(stats_variant & 6) && n_e_rows < 1000000 &&
-                           Mp <= 64;      // (M > 64: chip-filling rank updates, the hops do not matter and the old order is 3 % faster)
-    // (round 4, later) with the span fold on the scans (k_span_scan: 23 us instead of 72) and shares in the span-1 reductions the two
-    // branches are ~100 and ~77 us: the span > 1 branch is still the longer one and keeps the main stream (922 against 910 evals/s);
-    // SMCPP_STATS_VARIANT & 8 gives the main stream to the span-1 branch instead
-    const bool span_scan_off = opt().off(smcpp_opt::O_SPAN_SCAN);
-    const bool scan_fold = eigfree && ss_active && !span_scan_off;
-    const bool swap_main = crit_main && scan_fold && (stats_variant & 8);
-    hipStream_t se = crit_main ? (swap_main ? stream2 : s) : split_streams ? ((eigfree && (stats_variant & 1)) ? stream_hi : stream2) : s;
-    hipStream_t sp1 = crit_main ? (swap_main ? s : stream2) : s;          // the span-1 branch
-    // (scan chains: run_chains_ss has just recorded ev[3] behind the last pass - the fork event, without a second record)
-    hipEvent_t ev_fork = ss_active ? ev[3] : ev[8];
-    if (split_streams) {
-        if (!ss_active) HIPCHK(hipEventRecord(ev[8], s));
-        if (se != s) { HIPCHK(hipStreamWaitEvent(se, ev_fork, 0)); arena_wait(se); }
-        if (sp1 != s) { HIPCHK(hipStreamWaitEvent(sp1, ev_fork, 0)); arena_wait(sp1); }
+    hipLaunchKernelGGL(k_rank_acc<MODE>, dim3(nx, ny), dim3(64), 0, s, a);
+}
+
+// deterministic reduction of slab partials: ny ranges of len values, z shares each
+static void sum_parts(const double *part, const int *off, double *red, int len, unsigned ny, int z, hipStream_t s) {
+    hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(len, 256), ny, z), dim3(256), 0, s, part, off, red, len, z);
+}
+static int fin_blocks(int Mp, int K) { return ceil_div((long long)Mp * Mp, 256) + ceil_div((long long)(K + 1) * Mp, 256); }
+
+StatsPlan smcpp_im::resolve_stats_plan() {
+    using P = StatsPlan;
+    P p;
+    p.resolved = true;
+    const bool dual = dual_stream != 0;
+    // the span > 1 branch (weights, rank update, span fold or U / W products, Y) does not depend on the span-1 branch (weights, rank
+    // update, gamma sums): on two streams the short launches of one fill the gaps of the other
+    p.split = dual && !slabs_eg.empty();
+    // Eigen-free statistics of small inputs: the span > 1 rank update -> reduction -> span fold (2 x s_max serial steps) is the critical
+    // path, and a hop between two streams costs ~10 us (2 us between two kernels of one queue): THAT branch keeps the main stream,
+    // directly behind the chains and in front of the finalisation, and the span-1 branch (which has slack) forks.  (M > 64: chip-filling
+    // rank updates, the hops do not matter and the other order is 3 % faster.)
+    const bool crit_main = eigfree && p.split && n_e_rows < 1000000 && Mp <= 64;
+    p.span_gt1 = p.split && !crit_main ? P::SECOND : P::MAIN;
+    p.span1 = crit_main ? P::SECOND : P::MAIN;
+    // M <= 64, from half a million span-1 rows on: ONE pass over the key-sorted span-1 rows gives the rank update and the key's gamma
+    // sums from the same operands (k_rank_acc<3>): whole genome (3.6 M rows, bandwidth-bound) 3.77 -> 3.15 ms of statistics; one 100
+    // Mbp contig (129 k rows, latency-bound) 0.208 -> 0.225 ms - there the gamma sums stay a third concurrent branch, unless the span > 1
+    // branch holds the main stream: then ONE side branch beats two (887 against 873 evals/s).  SMCPP_S1_FUSE=0 / 1 forces either form.
+    p.s1_one_pass = Mp <= 64 && !save_gamma && !slabs_fk.empty() &&
+                    (opt().has(smcpp_opt::O_S1_FUSE) ? opt().i(smcpp_opt::O_S1_FUSE, 0) != 0 : (n_1_rows >= 500000 || crit_main));
+    // two kernels at M <= 64: k_rank_acc forms the span-1 weights itself, so the per-key gamma sums (k_s1_scalars + reduction) are a
+    // third independent branch; else, on two streams, they are reduced at the tail of the span > 1 branch (which finishes earlier)
+    const bool gsum_own = !p.s1_one_pass && dual && Mp <= 64 && !save_gamma && !slabs_sc.empty();
+    p.gsum_at = p.s1_one_pass ? P::GSUM_ONE_PASS : gsum_own ? P::GSUM_OWN_STREAM : p.split && !slabs_sc.empty() ? P::GSUM_SPAN_GT1_TAIL : P::GSUM_SPAN1;
+    p.gsum = gsum_own ? P::THIRD : p.span1;
+    // nothing in the statistics reads log_c: the log-likelihood runs on the third stream beside both branches (0.1 ms on un-binned
+    // data) - unless the span > 1 branch holds the main stream and the gamma sums the third: then at the head of the span-1 branch
+    const bool ll_own = p.split && !crit_main;            // (joined at the end of the main stream)
+    p.loglik = ll_own || (crit_main && p.s1_one_pass) ? P::THIRD : crit_main ? P::SECOND : P::MAIN;
+    // Mp > 128: operand rows staged through LDS (k_rank_acc_wide: a workgroup per 256 x 128 block of the output instead of a wavefront
+    // per 64 x 64 block; SMCPP_RANK_WIDE=0: k_rank_acc).  Teams of four slabs add their accumulators through LDS and write a quarter of
+    // the partial bytes (SMCPP_STATS_TEAM=0: one partial per slab).
+    const bool teams = stats_team_on();
+    p.rank = Mp > 128 && !opt().off(smcpp_opt::O_RANK_WIDE) ? P::RANK_WIDE : teams ? P::RANK_TEAMS : P::RANK_PER_SLAB;
+    p.teams_span1 = teams && !teams_rk.empty();
+    p.teams_one_pass = teams && !teams_fk.empty();
+    p.teams_span_gt1 = teams && eigfree && !teams_eg.empty();
+    if (eigfree) p.eigen = slabs_eg.empty() ? P::EIG_NONE : ss_active && !opt().off(smcpp_opt::O_SPAN_SCAN) ? P::EIG_FOLD_SCANS : P::EIG_FOLD_MATRIX_CORES;
+    else p.eigen = NT <= 4 && !slabs_eg.empty() ? P::EIG_GEN2 : P::EIG_CLASSIC;
+    // the span fold (tens of serial steps on a few CUs) ends the longest dependency chain, so what it waits for goes FIRST and alone
+    // (small inputs only: from ~10^6 span > 1 rows on, the two rank updates side by side finish sooner - whole genome 3.76 -> 3.36 ms)
+    p.rank_early = eigfree && p.split && n_e_rows < 1000000;
+    if (save_gamma && n_e_rows > 0) {
+        // long rows at 64 < M <= 256 with a structured T: eigen-power pieces + scan steps, which read the statistics' U / W products
+        // (main stream, behind them); the other forms need alpha, beta and the eigensystems only: beside the statistics
+        const bool pieces = !eigfree && NT > 4 && Mp <= 256 && !opt().off(smcpp_opt::O_GAMMA_PIECES) &&
+                            (double)gamma_piece_count() * Mp * 20.0 < 96e9 && (ss_active || ss_generators_only());
+        p.gamma_beside = dual && !pieces && !opt().off(smcpp_opt::O_GAMMA_SIDE);
+        p.gamma = p.gamma_beside ? P::HIGH : P::MAIN;
+        p.gamma_form = pieces ? P::GAMMA_PIECES : eigfree ? P::GAMMA_SCAN : NT <= 4 ? P::GAMMA_EIG_BATCHES : P::GAMMA_EIG_ROWS;
     }
-    // nothing in the statistics reads log_c any more (the span-1 weights take c itself): the two log-likelihood kernels
-    // ride on the eigen stream instead of heading the critical path of the main one
-    // ... and on a third stream when there is one: on un-binned data (a million rows per contig) they take 0.1 ms
-    // (which form the span-1 statistics take decides which streams are free: details where they are launched, below)
-    // M <= 64, from half a million span-1 rows on: ONE pass over the span-1 rows in key-sorted order, single-key slabs - the rank
-    // update and the key's gamma sums from the same operands (k_rank_acc<3>); k_s1_scalars and its second read of alpha / beta do
-    // not run.  Measured: whole genome (3.6 M span-1 rows, bandwidth-bound) 3.77 -> 3.15 ms of statistics; one 100 Mbp contig
-    // (129 k rows, one wavefront per SIMD, latency-bound) 0.208 -> 0.225 ms - there the gamma sums stay a third concurrent
-    // branch.  SMCPP_S1_FUSE=0 / 1 forces either form.
-    const bool kfuse = (Mp + 63) / 64 == 1 && !save_gamma && !slabs_fk.empty() &&
-                       (opt().has(smcpp_opt::O_S1_FUSE) ? opt().i(smcpp_opt::O_S1_FUSE, 0) != 0 : (n_1_rows >= 500000 || crit_main));
-    // (round 4: with the span > 1 branch on the main stream the span-1 statistics are ONE side branch in the one-pass form instead
-    // of two - 887 against 873 headline evals per second, and 140 MB less traffic per E-step)
-    // (eigen-free with the span > 1 branch on the main stream: free at its head, which waits there; round 5: the other eigen-free cases -
-    // M > 64, or a million span > 1 rows - no longer make the main stream wait, so the two kernels would delay its weights pass by their
-    // 60 - 130 us: third stream there too)
-    const bool ll_own = split_streams && stream3 != nullptr && (!eigfree || !crit_main);
-    // crit_main with the one-pass span-1 form: the third stream has nothing else to do - the log-likelihood kernels run there,
-    // beside both branches instead of at the head of the span-1 branch (joined in front of the finalisation)
-    const bool ll3 = crit_main && kfuse && stream3 != nullptr;
-    hipStream_t sl = (ll_own || ll3) ? stream3 : (crit_main ? sp1 : eigfree ? s : se);   // (the eigen-free branch is the longer one)
-    if (ll_own || ll3) { HIPCHK(hipStreamWaitEvent(sl, ev_fork, 0)); arena_wait(sl); }
-    hipLaunchKernelGGL(k_loglik_partial, dim3(llblk, n_contigs), dim3(256), 0, sl, la);
-    hipLaunchKernelGGL(k_loglik_final, dim3(n_contigs), dim3(256), 0, sl, la);
-    if (ll_own || ll3) HIPCHK(hipEventRecord(ev[19], sl));
-    FinArgs fa;
-    fa.M = M; fa.Mp = Mp; fa.K = K; fa.G = G; fa.Ke = Ke; fa.n_contigs = n_contigs;
-    fa.eb_slab_off = d_eb_slab_off.p; fa.eb_gid = d_eb_gid.p; fa.ce_bucket_off = d_ce_bucket_off.p;
-    fa.s1_slab_off = d_s1_slab_off.p; fa.gk_slab_off = d_gk_slab_off.p; fa.g_span = d_g_span.p;
-    fa.e_kid = d_e_kid.p; fa.dsc = d_dsc.p; fa.dun = d_dun.p; fa.Prm = d_Prm.p; fa.Pinvrm = d_Pinvrm.p;
-    fa.E = d_E.p; fa.Td = d_Td.p; fa.ZS = ZS; fa.red_e = nullptr; fa.red_1 = d_red_1.p; fa.red_g = d_red_g.p; fa.ZG = kfuse ? ZG : 1;
-    fa.alpha = d_alpha.p; fa.beta = d_beta.p; fa.contig_base = d_contig_base.p;
-    fa.Z = d_Z.p; fa.Y = d_Y.p; fa.xisum = d_xisum.p; fa.gsum = d_gsum.p; fa.gamma0 = d_gamma0.p;
-    fa.dpow = d_dpow.p;
-    fa.part_e = nullptr;
+    // the finalisation signals the host itself when nothing follows it on the main stream and the launch is small: every block ends
+    // with a device-scope fence and an atomic on ONE counter (1 500 contigs: 3.2 ms; beyond 128 blocks the one-thread kernel signals)
+    p.fin_signals = !save_gamma && !ll_own && (long long)fin_blocks(Mp, K) * n_contigs <= 128;
+    return p;
+}
+
+// A side stream forks off the chains' end and waits for the parameter arena copied beside them as well: its kernels read the log-scales
+// and the emission table (a wait in front of the fork event instead costs 12 us per eval: every branch then starts behind the barrier
+// packet; on the side streams, which have slack, it costs nothing measurable)
+void smcpp_im::fork_from_chains(hipStream_t x) {
+    HIPCHK(hipStreamWaitEvent(x, ev[ss_active ? EV_CHAINS_END : EV_STATS_FORK], 0));
+    if (arena_side) HIPCHK(hipStreamWaitEvent(x, ev[EV_ARENA], 0));
+}
+
+// weights (and, span-1 rows, partial gamma sums and save_gamma's rows) of the span-1 rows, or only the weights of the span > 1 rows
+S1Args smcpp_im::s1_args(bool span_gt1) {
+    S1Args a;
+    a.M = M; a.Mp = Mp;
+    a.nslabs = (int)(span_gt1 ? slabs_eg.size() : slabs_sc.size()); a.slabs = span_gt1 ? d_slabs_eg.p : d_slabs_sc.p;
+    a.perm = span_gt1 ? d_perme.p : d_perm1.p;
+    a.alpha = d_alpha.p; a.beta = d_beta.p; a.cnorm = d_cnorm.p; a.w1 = d_w1.p; a.gpart = d_gpart.p;
+    a.gamma_rows = !span_gt1 && save_gamma ? d_gamma_rows.p : nullptr;
+    a.only_w1 = span_gt1 ? 1 : 0;
+    return a;
+}
+
+AccArgs smcpp_im::acc_args(const std::vector<Slab> &sl, const Slab *d_sl, const int *perm, const int2 *permk, double *part, double *gpart) {
+    AccArgs a;
+    a.M = M; a.Mp = Mp; a.NB = (Mp + 63) / 64; a.rowinfo = d_rowinfo.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
+    a.w1 = d_w1.p; a.cnorm = d_cnorm.p; a.E = d_E.p; a.Xs = d_Xs.p; a.Ys = d_Ys.p;
+    a.nslabs = (int)sl.size(); a.slabs = d_sl; a.perm = perm; a.permk = permk; a.part = part; a.gpart = gpart; a.teams = nullptr;
+    return a;
+}
+
+// weights of the span > 1 rows (M <= 64: k_rank_acc<2> forms them itself), then their rank update per (span, key) group
+void smcpp_im::launch_span_gt1_rank(const StatsPlan &p) {
+    const hipStream_t se = plan_stream(p.span_gt1);
+    if (Mp > 64) launch_s1(NPL, s1_args(true), se);
+    launch_rank_acc<2>(acc_args(slabs_eg, d_slabs_eg.p, d_perme.p, nullptr, d_part_e.p, nullptr), p.rank == StatsPlan::RANK_WIDE,
+                       p.teams_span_gt1 ? d_teams_eg.p : nullptr, teams_eg.size(), se);
+}
+
+void smcpp_im::launch_span1_branch(const StatsPlan &p) {
+    const hipStream_t sp1 = plan_stream(p.span1), sg1 = plan_stream(p.gsum);
     const int MMi = Mp * Mp;
-    const int nb2 = ceil_div((long long)Mp * Mp, 256);
-    AccArgs aa;
-    aa.M = M; aa.Mp = Mp; aa.NB = (Mp + 63) / 64; aa.rowinfo = d_rowinfo.p; aa.alpha = d_alpha.p; aa.beta = d_beta.p;
-    aa.w1 = d_w1.p; aa.cnorm = d_cnorm.p; aa.E = d_E.p; aa.Xs = d_Xs.p; aa.Ys = d_Ys.p;
-    aa.gpart = nullptr; aa.teams = nullptr;
-    // (round 5) teams of four slabs reduce their accumulators through LDS: a quarter of the partial bytes (SMCPP_STATS_TEAM=0: one
-    // partial per slab, as in rounds 2-4)
-    const bool team_env = stats_team_on();
-    const bool team2 = team_env && eigfree && !teams_eg.empty();
-    const bool team3 = team_env && !teams_fk.empty();
-    const bool team0 = team_env && !teams_rk.empty();
-    // (round 6) Mp > 128: the rank updates of modes 0 / 2 stage their operand rows through LDS (kernels.hpp: k_rank_acc_wide - one
-    // workgroup per team and 256 x 128 block of the output instead of one wavefront per slab and 64 x 64 block); SMCPP_RANK_WIDE=0:
-    // the per-wavefront form
-    const bool rank_wide = Mp > 128 && !opt().off(smcpp_opt::O_RANK_WIDE);
-    auto launch_wide = [&](int mode, const AccArgs &ar, unsigned gx, hipStream_t st) {
-        static bool once = false;
-        if (!once) {
-            HIPCHK(hipFuncSetAttribute((const void *)k_rank_acc_wide<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHK(hipFuncSetAttribute((const void *)k_rank_acc_wide<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHK(hipFuncSetAttribute((const void *)k_rank_acc_wide<0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            HIPCHK(hipFuncSetAttribute((const void *)k_rank_acc_wide<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            once = true;
-        }
-        const dim3 grid(gx, (unsigned)(((Mp + 255) / 256) * ((Mp + 127) / 128)));
-        const bool four = opt().i(smcpp_opt::O_RANK_WIDE, 8) == 4;      // (SMCPP_RANK_WIDE=4: one wavefront per SIMD)
-        if (four) {
-            if (mode == 0) hipLaunchKernelGGL((k_rank_acc_wide<0, 4>), grid, dim3(256), RW_LDS, st, ar);
-            else hipLaunchKernelGGL((k_rank_acc_wide<2, 4>), grid, dim3(256), RW_LDS, st, ar);
-        } else {
-            if (mode == 0) hipLaunchKernelGGL((k_rank_acc_wide<0, 8>), grid, dim3(512), RW_LDS, st, ar);
-            else hipLaunchKernelGGL((k_rank_acc_wide<2, 8>), grid, dim3(512), RW_LDS, st, ar);
-        }
-    };
-    // Eigen-free statistics: the span fold (tens of serial steps on a few CUs) ends the longest dependency chain of the
-    // phase, so what it waits for - the rank accumulation of the span > 1 rows - goes FIRST and alone; the span-1 branches start
-    // behind it and run while the fold does
-    // (small inputs only: from ~10^6 span > 1 rows on, the rank updates are bound by memory parallelism and the two of them
-    // running side by side finish sooner than one after the other - whole genome: 3.76 -> 3.36 ms of statistics)
-    const bool rank2_early = eigfree && split_streams && !slabs_eg.empty() && !(stats_variant & 2) && n_e_rows < 1000000;
-    bool wait17 = false;
-    const bool eig_gen2 = !eigfree && NT <= 4 && !slabs_eg.empty();      // (M > 64: the two-kernel form below)
-    if (!slabs_eg.empty() && !eig_gen2) {
-        d_part_e.alloc(std::max<size_t>(1, team2 ? teams_eg.size() : slabs_eg.size()) * Mp * Mp);
-        fa.part_e = d_part_e.p;
-        if (eigfree) { d_red_e.alloc(std::max<size_t>(1, eb_gid.size()) * Mp * Mp); fa.red_e = d_red_e.p; }
+    if (p.gsum_at == StatsPlan::GSUM_OWN_STREAM) {
+        if (p.span1 == StatsPlan::SECOND) fork_from_chains(stream3);     // (forks where the span-1 branch does)
+        else hand_over(EV_GSUM_FORK, stream, stream3);
     }
-    if (rank2_early) {
-        if (aa.NB != 1) {
-            S1Args se_a;
-            se_a.M = M; se_a.Mp = Mp; se_a.nslabs = (int)slabs_eg.size(); se_a.slabs = d_slabs_eg.p; se_a.perm = d_perme.p;
-            se_a.alpha = d_alpha.p; se_a.beta = d_beta.p; se_a.cnorm = d_cnorm.p; se_a.w1 = d_w1.p; se_a.gpart = d_gpart.p;
-            se_a.gamma_rows = nullptr; se_a.only_w1 = 1;
-            launch_s1(NPL, se_a, se);
-        }
-        AccArgs ae = aa;
-        ae.nslabs = (int)slabs_eg.size(); ae.slabs = d_slabs_eg.p; ae.perm = d_perme.p; ae.part = d_part_e.p;
-        if (team2) ae.teams = d_teams_eg.p;
-        if (rank_wide) launch_wide(2, ae, team2 ? (unsigned)teams_eg.size() : (unsigned)ae.nslabs, se);
-        else if (team2)
-            hipLaunchKernelGGL((k_rank_acc<2, true>), dim3((unsigned)teams_eg.size(), ae.NB * ae.NB), dim3(256), 0, se, ae);
-        else
-        hipLaunchKernelGGL(k_rank_acc<2>, dim3(ae.nslabs, ae.NB * ae.NB), dim3(64), 0, se, ae);
-        if (!crit_main) {
-            // (round 5) the span-1 branch waits for this rank update only where its OWN rank update starts: its weights pass
-            // (k_s1_scalars, bound by memory round trips) runs beside the weights pass and the head of the rank update of this branch
-            HIPCHK(hipEventRecord(ev[17], se));
-            wait17 = true;
-        }
+    if (!p.s1_one_pass && !slabs_sc.empty()) {
+        launch_s1(NPL, s1_args(false), sg1);
+        if (p.gsum_at == StatsPlan::GSUM_OWN_STREAM) {
+            sum_parts(d_gpart.p, d_gk_slab_off.p, d_red_g.p, Mp, n_contigs * K, 1, sg1);
+            HIPCHK(hipEventRecord(ev[EV_GSUM_DONE], sg1));
+        } else if (p.gsum_at == StatsPlan::GSUM_SPAN_GT1_TAIL) HIPCHK(hipEventRecord(ev[EV_S1_SCALARS], sp1));
     }
-    // ---- span-1 branch (main stream) ----
-    // M <= 64: k_rank_acc forms the weights itself, so the per-key gamma sums (k_s1_scalars + their reduction) are a third
-    // independent branch: own stream, joined before the finalisation
-    const bool s1_own = !kfuse && dual_stream && stream3 != nullptr && (Mp + 63) / 64 == 1 && !save_gamma && !slabs_sc.empty();
-    hipStream_t s1s = s1_own ? stream3 : sp1;
-    if (s1_own) {
-        if (crit_main) { HIPCHK(hipStreamWaitEvent(s1s, ev_fork, 0)); arena_wait(s1s); }     // (forks where the span-1 branch does: at the chains' end)
-        else {
-            HIPCHK(hipEventRecord(ev[15], s));
-            HIPCHK(hipStreamWaitEvent(s1s, ev[15], 0));
-        }
-    }
-    if (!slabs_sc.empty() && !kfuse) {
-        S1Args sa;
-        sa.M = M; sa.Mp = Mp; sa.nslabs = (int)slabs_sc.size(); sa.slabs = d_slabs_sc.p; sa.perm = d_perm1.p;
-        sa.alpha = d_alpha.p; sa.beta = d_beta.p; sa.cnorm = d_cnorm.p; sa.w1 = d_w1.p; sa.gpart = d_gpart.p;
-        sa.gamma_rows = save_gamma ? d_gamma_rows.p : nullptr;
-        sa.only_w1 = 0;
-        launch_s1(NPL, sa, s1s);
-        if (s1_own) {
-            hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(Mp, 256), n_contigs * K, 1), dim3(256), 0, s1s,
-                               (const double *)d_gpart.p, (const int *)d_gk_slab_off.p, d_red_g.p, Mp, 1);
-            HIPCHK(hipEventRecord(ev[16], s1s));
-        } else if (split_streams) HIPCHK(hipEventRecord(ev[14], sp1));
-    }
-    if (wait17) HIPCHK(hipStreamWaitEvent(sp1, ev[17], 0));
-    if (kfuse) {
-        d_part_1.alloc(std::max<size_t>(1, team3 ? teams_fk.size() : slabs_fk.size()) * Mp * Mp);
+    // the span > 1 rank update launched early on the side stream: the span-1 branch waits for it only where its OWN rank update
+    // starts - its weights pass (k_s1_scalars, bound by memory round trips) runs beside the head of that rank update
+    if (p.rank_early && p.span1 == StatsPlan::MAIN) HIPCHK(hipStreamWaitEvent(sp1, ev[EV_RANK2_DONE], 0));
+    if (p.s1_one_pass) {
+        d_part_1.alloc(std::max<size_t>(1, p.teams_one_pass ? teams_fk.size() : slabs_fk.size()) * Mp * Mp);
         d_gpart_fk.alloc(slabs_fk.size() * Mp);
-        aa.nslabs = (int)slabs_fk.size(); aa.slabs = d_slabs_fk.p; aa.perm = d_perm1.p; aa.permk = nullptr; aa.part = d_part_1.p;
-        aa.gpart = d_gpart_fk.p;
-        if (team3) {
-            aa.teams = d_teams_fk.p;
-            hipLaunchKernelGGL((k_rank_acc<3, true>), dim3((unsigned)teams_fk.size(), 1), dim3(256), 0, sp1, aa);
-        } else
-        hipLaunchKernelGGL(k_rank_acc<3>, dim3(aa.nslabs, 1), dim3(64), 0, sp1, aa);
-        hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(Mp, 256), n_contigs * K, ZG), dim3(256), 0, sp1,
-                           (const double *)d_gpart_fk.p, (const int *)d_fk_gk_off.p, d_red_g.p, Mp, ZG);
-        hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(MMi, 256), n_contigs, ZS), dim3(256), 0, sp1,
-                           (const double *)d_part_1.p, (const int *)(team3 ? d_fk_c_team_off.p : d_fk_c_off.p), d_red_1.p, MMi, ZS);
-    } else
-    if (!slabs_rk.empty()) {
-        aa.nslabs = (int)slabs_rk.size(); aa.slabs = d_slabs_rk.p; aa.perm = d_perm1.p; aa.permk = d_perm1k.p; aa.part = d_part_1.p;
-        if (team0) aa.teams = d_teams_rk.p;
-        if (rank_wide) launch_wide(0, aa, team0 ? (unsigned)teams_rk.size() : (unsigned)aa.nslabs, sp1);
-        else if (team0)
-            hipLaunchKernelGGL((k_rank_acc<0, true>), dim3((unsigned)teams_rk.size(), aa.NB * aa.NB), dim3(256), 0, sp1, aa);
-        else
-        hipLaunchKernelGGL(k_rank_acc<0>, dim3(aa.nslabs, aa.NB * aa.NB), dim3(64), 0, sp1, aa);
+        launch_rank_acc<3>(acc_args(slabs_fk, d_slabs_fk.p, d_perm1.p, nullptr, d_part_1.p, d_gpart_fk.p), false,
+                           p.teams_one_pass ? d_teams_fk.p : nullptr, teams_fk.size(), sp1);
+        sum_parts(d_gpart_fk.p, d_fk_gk_off.p, d_red_g.p, Mp, n_contigs * K, ZG, sp1);
+        sum_parts(d_part_1.p, p.teams_one_pass ? d_fk_c_team_off.p : d_fk_c_off.p, d_red_1.p, MMi, n_contigs, ZS, sp1);
+    } else {
+        if (!slabs_rk.empty())
+            launch_rank_acc<0>(acc_args(slabs_rk, d_slabs_rk.p, d_perm1.p, d_perm1k.p, d_part_1.p, nullptr), p.rank == StatsPlan::RANK_WIDE,
+                               p.teams_span1 ? d_teams_rk.p : nullptr, teams_rk.size(), sp1);
+        if (p.gsum_at == StatsPlan::GSUM_SPAN1) sum_parts(d_gpart.p, d_gk_slab_off.p, d_red_g.p, Mp, n_contigs * K, 1, sp1);
+        sum_parts(d_part_1.p, p.teams_span1 ? d_s1_team_off.p : d_s1_slab_off.p, d_red_1.p, MMi, n_contigs, ZS, sp1);
     }
-    // the per-key gamma sums only need the span-1 scalars: with two streams their reduction runs at the tail of the eigen
-    // stream (which finishes earlier) instead of between the two rank-update kernels of the main one
-    const bool gsum_on_se = split_streams && !slabs_sc.empty() && !s1_own && !kfuse;
-    if (!gsum_on_se && !s1_own && !kfuse)
-        hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(Mp, 256), n_contigs * K, 1), dim3(256), 0, sp1,
-                           (const double *)d_gpart.p, (const int *)d_gk_slab_off.p, d_red_g.p, Mp, 1);
-    if (!kfuse)
-    hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(MMi, 256), n_contigs, ZS), dim3(256), 0, sp1,
-                       (const double *)d_part_1.p, (const int *)(team0 ? d_s1_team_off.p : d_s1_slab_off.p), d_red_1.p, MMi, ZS);
-    HIPCHK(hipEventRecord(ev[4], sp1));
-    // ---- eigen branch (second stream when available) ----
-    fa.eigfree = eigfree ? 1 : 0;
-    if (!slabs_eg.empty() && eigfree) {
-        // weights of the span > 1 rows (as those of the span-1 rows), rank accumulation per (span, key) group, deterministic
-        // reduction of the slab partials, then the span fold per (contig, key)
-        S1Args se_a;
-        se_a.M = M; se_a.Mp = Mp; se_a.nslabs = (int)slabs_eg.size(); se_a.slabs = d_slabs_eg.p; se_a.perm = d_perme.p;
-        se_a.alpha = d_alpha.p; se_a.beta = d_beta.p; se_a.cnorm = d_cnorm.p; se_a.w1 = d_w1.p; se_a.gpart = d_gpart.p;
-        se_a.gamma_rows = nullptr; se_a.only_w1 = 1;
-        if (!rank2_early) {
-            if (aa.NB != 1) launch_s1(NPL, se_a, se);          // M <= 64: k_rank_acc<2> forms the weights itself
-            AccArgs ae = aa;
-            ae.nslabs = (int)slabs_eg.size(); ae.slabs = d_slabs_eg.p; ae.perm = d_perme.p; ae.part = d_part_e.p;
-            if (team2) ae.teams = d_teams_eg.p;
-            if (rank_wide) launch_wide(2, ae, team2 ? (unsigned)teams_eg.size() : (unsigned)ae.nslabs, se);
-            else if (team2)
-                hipLaunchKernelGGL((k_rank_acc<2, true>), dim3((unsigned)teams_eg.size(), ae.NB * ae.NB), dim3(256), 0, se, ae);
-            else
-            hipLaunchKernelGGL(k_rank_acc<2>, dim3(ae.nslabs, ae.NB * ae.NB), dim3(64), 0, se, ae);
-        }
+    HIPCHK(hipEventRecord(ev[EV_SPAN1_DONE], sp1));
+}
+
+void smcpp_im::launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa) {
+    const hipStream_t se = plan_stream(p.span_gt1);
+    const int MMi = Mp * Mp, nb2 = ceil_div((long long)Mp * Mp, 256);
+    switch (p.eigen) {
+    case StatsPlan::EIG_NONE: break;
+    case StatsPlan::EIG_FOLD_SCANS:
+    case StatsPlan::EIG_FOLD_MATRIX_CORES:
+        // weights and rank update per (span, key) group (unless launched early), deterministic reduction of the slab partials, then
+        // the span fold per (contig, key)
+        if (!p.rank_early) launch_span_gt1_rank(p);
         if (!eb_gid.empty())                                     // ONE share per bucket: k_span_F reads it on its serial path
-            hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(MMi, 256), (unsigned)eb_gid.size(), 1), dim3(256), 0, se,
-                               (const double *)d_part_e.p, (const int *)(team2 ? d_eb_team_off.p : d_eb_slab_off.p), d_red_e.p, MMi, 1);
-        const size_t shm = (size_t)2 * Mp * (Mp + 1) * sizeof(double);
-        // SMCPP_SPAN_FH=1: the one-workgroup-per-(contig, key) fold (M <= 64) instead of the strip kernels
-        // (round 4) the fold on the SCANS: a row of F times A / A times a column of H is one O(M) step of the backward / forward chain
-        // operator, so one wavefront per row / column walks all s_max steps on its own (chains_ss.hpp: k_span_scan) - no matrix
-        // product, no barrier.  SMCPP_SPAN_SCAN=0: the matrix-core strips of round 3.
-        if (scan_fold) {
-            d_Fall.alloc((size_t)n_contigs * Ke * ss_max_span * Mp * Mp);
+            sum_parts(d_part_e.p, p.teams_span_gt1 ? d_eb_team_off.p : d_eb_slab_off.p, d_red_e.p, MMi, (unsigned)eb_gid.size(), 1, se);
+        d_Fall.alloc((size_t)n_contigs * Ke * ss_max_span * Mp * Mp);
+        if (p.eigen == StatsPlan::EIG_FOLD_SCANS) {
+            // a row of F times A / A times a column of H is one O(M) step of the backward / forward chain operator, so one wavefront
+            // per row / column walks all s_max steps on its own - no matrix product, no barrier
             const int nwav = n_contigs * Ke * M;
             const dim3 grid(ceil_div(nwav, 4)), block(256);
             switch (NPL) {
@@ -1058,9 +947,7 @@ void smcpp_im::enqueue_stats() {
 #undef SC_
             }
         } else {
-            // the fold on the matrix cores (round 3; SMCPP_SPAN_SCAN=0 or no scan chains): strips of 16 rows (F) / columns (H), one
-            // workgroup each, F_t through scratch
-            d_Fall.alloc((size_t)n_contigs * Ke * ss_max_span * Mp * Mp);
+            // strips of 16 rows (F) / columns (H), one workgroup each, F_t through scratch
             const int nstrip = NT, nwg = n_contigs * Ke * nstrip;
 #define B_(x) { hipLaunchKernelGGL((k_span_big<x, 0>), dim3(nwg), dim3(64 * x), 0, se, fa, ss_max_span, d_Fall.p); \
                 hipLaunchKernelGGL((k_span_big<x, 1>), dim3(nwg), dim3(64 * x), 0, se, fa, ss_max_span, d_Fall.p); }
@@ -1068,9 +955,9 @@ void smcpp_im::enqueue_stats() {
             else if (NT <= 8) B_(8) else if (NT <= 12) B_(12) else B_(16)
 #undef B_
         }
-    }
-    if (eig_gen2) {
-        // generation 2 (M <= 64): slabs that mix span groups, the span-Q weighting inside the accumulation (k_eig_fused2)
+        break;
+    case StatsPlan::EIG_GEN2: {
+        // slabs that mix span groups, the span-Q weighting inside the accumulation
         UWArgs ua;
         ua.M = M; ua.Mp = Mp; ua.nslabs = (int)slabs_ek.size(); ua.slabs = d_slabs_ek.p; ua.perm = d_perme.p;
         ua.alpha = d_alpha.p; ua.beta = d_beta.p; ua.g_eig = d_g_eig.p; ua.g_scale = d_g_scale.p;
@@ -1087,171 +974,224 @@ void smcpp_im::enqueue_stats() {
         const int nblk = ceil_div(ua.nslabs, 4);
         const size_t shm = (size_t)2 * (16 * NT) * (16 * NT + 1) * sizeof(double);
         switch (NT) {
-#define F_(x) case x: { static bool once = false; if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_eig_fused2<x>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; } \
-                    hipLaunchKernelGGL(k_eig_fused2<x>, dim3(nblk), dim3(256), shm, se, ua, d_part_ek.p); } break;
+#define F_(x) case x: lds_limit_once<k_eig_fused2<x>>(); hipLaunchKernelGGL(k_eig_fused2<x>, dim3(nblk), dim3(256), shm, se, ua, d_part_ek.p); break;
             F_(1) F_(2) F_(3)
             default: F_(4)
 #undef F_
         }
-        hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(LEN, 256), (unsigned)nce, nsh), dim3(256), 0, se,
-                           (const double *)d_part_ek.p, (const int *)d_ek_slab_off.p, d_red_ek.p, LEN, nsh);
+        sum_parts(d_part_ek.p, d_ek_slab_off.p, d_red_ek.p, LEN, (unsigned)nce, nsh, se);
         hipLaunchKernelGGL(k_fin_Z2, dim3(nb2, nce), dim3(256), 0, se, fa, (const double *)d_red_ek.p, nsh);
         hipLaunchKernelGGL(k_fin_Y, dim3(nb2, nce), dim3(256), 0, se, fa);
+        break;
     }
-    if (!slabs_eg.empty() && !eigfree && !eig_gen2) {
-        UWArgs ua;
-        ua.M = M; ua.Mp = Mp; ua.nslabs = (int)slabs_eg.size(); ua.slabs = d_slabs_eg.p; ua.perm = d_perme.p;
-        ua.alpha = d_alpha.p; ua.beta = d_beta.p; ua.g_eig = d_g_eig.p; ua.g_scale = d_g_scale.p;
-        ua.dpow = d_dpow.p; ua.PinvT = d_PinvT.p; ua.Prm = d_Prm.p; ua.Xs = d_Xs.p; ua.Ys = d_Ys.p; ua.pos_gid = nullptr; ua.g_span = nullptr;
-        {
+    case StatsPlan::EIG_CLASSIC:
+        if (!slabs_eg.empty()) {
+            UWArgs ua;
+            ua.M = M; ua.Mp = Mp; ua.nslabs = (int)slabs_eg.size(); ua.slabs = d_slabs_eg.p; ua.perm = d_perme.p;
+            ua.alpha = d_alpha.p; ua.beta = d_beta.p; ua.g_eig = d_g_eig.p; ua.g_scale = d_g_scale.p;
+            ua.dpow = d_dpow.p; ua.PinvT = d_PinvT.p; ua.Prm = d_Prm.p; ua.Xs = d_Xs.p; ua.Ys = d_Ys.p; ua.pos_gid = nullptr; ua.g_span = nullptr;
             launch_uw(NT, ua, se);
-            AccArgs ae = aa;
-            ae.nslabs = (int)slabs_eg.size(); ae.slabs = d_slabs_eg.p; ae.perm = d_perme.p; ae.part = d_part_e.p;
-            hipLaunchKernelGGL(k_rank_acc<1>, dim3(ae.nslabs, ae.NB * ae.NB), dim3(64), 0, se, ae);
+            // (no reduction pass over the slab partials: k_fin_Z sums the slabs of a bucket itself)
+            launch_rank_acc<1>(acc_args(slabs_eg, d_slabs_eg.p, d_perme.p, nullptr, d_part_e.p, nullptr), false, nullptr, 0, se);
         }
-        // (no reduction pass over the slab partials: k_fin_Z sums the slabs of a bucket itself)
-    }
-    if (Ke > 0 && !eigfree && !eig_gen2) {
-        // slices of the groups of one (contig, key): enough blocks to fill the chip when there are many groups
-        int max_b = 0;
-        for (size_t ce = 0; ce + 1 < ce_bucket_off.size(); ++ce) max_b = std::max(max_b, ce_bucket_off[ce + 1] - ce_bucket_off[ce]);
-        const int nsl = std::max(1, std::min(std::min(256, max_b), 2048 / std::max(1, nb2 * n_contigs * Ke)));
-        if (nsl > 1) { d_Zpart.alloc((size_t)nsl * n_contigs * Ke * Mp * Mp); fa.Zpart = d_Zpart.p; }
-        else fa.Zpart = nullptr;
-        hipLaunchKernelGGL(k_fin_Z, dim3(nb2, n_contigs * Ke, nsl), dim3(256), 0, se, fa);
-        if (nsl > 1) hipLaunchKernelGGL(k_fin_Zsum, dim3(nb2, n_contigs * Ke), dim3(256), 0, se, fa, nsl, n_contigs * Ke);
-        hipLaunchKernelGGL(k_fin_Y, dim3(nb2, n_contigs * Ke), dim3(256), 0, se, fa);
-    }
-    if (gsum_on_se) {
-        HIPCHK(hipStreamWaitEvent(se, ev[14], 0));
-        hipLaunchKernelGGL(k_sum_parts, dim3(ceil_div(Mp, 256), n_contigs * K, 1), dim3(256), 0, se,
-                           (const double *)d_gpart.p, (const int *)d_gk_slab_off.p, d_red_g.p, Mp, 1);
-    }
-    if (crit_main) {
-        // (the third stream joins the side stream, and the main stream waits for ONE event: every wait is a barrier packet of a few
-        // microseconds on the queue it is put on, signalled or not)
-        hipStream_t side = swap_main ? se : sp1;
-        if (ll3) HIPCHK(hipStreamWaitEvent(side, ev[19], 0));
-        HIPCHK(hipEventRecord(ev[9], side));
-        HIPCHK(hipStreamWaitEvent(s, ev[9], 0));
-    } else if (split_streams) {
-        HIPCHK(hipEventRecord(ev[9], se));
-        HIPCHK(hipStreamWaitEvent(s, ev[9], 0));
-    }
-    if (s1_own) HIPCHK(hipStreamWaitEvent(s, ev[16], 0));
-    {
-        const int nbf = nb2 + ceil_div((long long)(K + 1) * Mp, 256);
-        // nothing follows the finalisation on this stream when gamma rows are not asked for: its last block signals the host
-        // (only while the launch is small: every block ends with a device-scope fence and an atomic on ONE counter - 40 500 blocks of
-        // 1 500 contigs took 3.2 ms for it, 80 ns each, tools/many_contigs_probe.py; beyond 128 blocks the one-thread kernel signals: 100 contigs 0.37 -> 0.20 ms of finalisation, 22 contigs 0.049 -> 0.03)
-        done_folded = fold_done_epoch != 0 && !save_gamma && !ll_own && (long long)nbf * n_contigs <= 128;
-        if (done_folded) {
-            if (!d_fin_ctr.p) { d_fin_ctr.alloc(1); HIPCHK(hipMemsetAsync(d_fin_ctr.p, 0, sizeof(unsigned), s)); fin_target = 0; }
-            fin_target += (unsigned)nbf * (unsigned)n_contigs;
+        if (Ke > 0) {
+            // slices of the groups of one (contig, key): enough blocks to fill the chip when there are many groups
+            int max_b = 0;
+            for (size_t ce = 0; ce + 1 < ce_bucket_off.size(); ++ce) max_b = std::max(max_b, ce_bucket_off[ce + 1] - ce_bucket_off[ce]);
+            const int nsl = std::max(1, std::min(std::min(256, max_b), 2048 / std::max(1, nb2 * n_contigs * Ke)));
+            if (nsl > 1) { d_Zpart.alloc((size_t)nsl * n_contigs * Ke * Mp * Mp); fa.Zpart = d_Zpart.p; }
+            else fa.Zpart = nullptr;
+            hipLaunchKernelGGL(k_fin_Z, dim3(nb2, n_contigs * Ke, nsl), dim3(256), 0, se, fa);
+            if (nsl > 1) hipLaunchKernelGGL(k_fin_Zsum, dim3(nb2, n_contigs * Ke), dim3(256), 0, se, fa, nsl, n_contigs * Ke);
+            hipLaunchKernelGGL(k_fin_Y, dim3(nb2, n_contigs * Ke), dim3(256), 0, se, fa);
         }
-        hipLaunchKernelGGL(k_fin_both, dim3(nbf, n_contigs), dim3(256), 0, s, fa, nb2, d_fin_ctr.p, fin_target,
-                           done_folded ? d_done_view : (int *)nullptr, fold_done_epoch);
+        break;
     }
-    if (save_gamma && n_e_rows > 0) {
-        hipStream_t sg = gamma_side ? stream_hi : s;
-        GammaRowArgs ga;
-        ga.M = M; ga.Mp = Mp; ga.nrows = (int)n_e_rows; ga.perm = d_perme.p; ga.row_slab = d_erow_slab.p;
-        ga.slabs = d_slabs_eg.p; ga.g_eig = d_g_eig.p; ga.g_span = d_g_span.p; ga.dun = d_dun.p; ga.dsc = d_dsc.p; ga.dpow = d_dpow.p;
-        ga.Prm = d_Prm.p; ga.Pinvrm = d_Pinvrm.p; ga.PinvT = d_PinvT.p; ga.Sq = nullptr;
-        ga.alpha = d_alpha.p; ga.beta = d_beta.p; ga.gamma_rows = d_gamma_rows.p; ga.erow_desc = d_erow_desc.p;
-        const bool mfma_rows = NT <= 4;          // (M > 64: the scalar kernel on a span-Q table in memory)
-        gamma_pieces_last = false;
-        if (gamma_pieces) {
-            // (round 6) long rows at 64 < M <= 256: eigen-power pieces + scan steps (chains_ss.hpp: k_piece_vectors)
-            build_gamma_pieces();
-            const int MS = 64 * NPL;
-            d_gp_gen.upload(ss_gen, sg);
-            d_gp_cs.alloc((size_t)Ke * 2 * Mp);
-            d_gp_l2d.alloc((size_t)Ke * Mp);
-            const size_t npc = gp_pieces.size();
-            d_gp_pvf.alloc(npc * Mp); d_gp_pvb.alloc(npc * Mp); d_gp_pgam.alloc(npc * Mp);
-            PieceArgs pa;
-            pa.M = M; pa.Mp = Mp; pa.npieces = (int)npc; pa.ntiles = (int)gp_tiles.size();
-            pa.pieces = d_gp_pieces.p; pa.tiles = d_gp_tiles.p; pa.Xs = d_Xs.p; pa.Ys = d_Ys.p; pa.dsc = d_dsc.p;
-            pa.PT = d_PT.p; pa.Pinvrm = d_Pinvrm.p; pa.cs = d_gp_cs.p; pa.l2d = d_gp_l2d.p; pa.pvf = d_gp_pvf.p; pa.pvb = d_gp_pvb.p; pa.pgam = d_gp_pgam.p;
-            hipLaunchKernelGGL(k_piece_rowsums, dim3(ceil_div(Ke * 2 * Mp, 256)), dim3(256), 0, sg, Ke, Mp, (const double *)d_PT.p,
-                               (const double *)d_Pinvrm.p, d_gp_cs.p, (const double *)d_dsc.p, d_gp_l2d.p);
-            if (pa.ntiles > 0) {
-                static bool once = false;
-                if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_piece_vectors, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; }
-                const size_t shm = (size_t)4 * 16 * (Mp + 4) * sizeof(double);
-                const int nblk = std::min(2 * ceil_div(pa.ntiles, 4), 2048);
-                hipLaunchKernelGGL(k_piece_vectors, dim3(nblk), dim3(256), shm, sg, pa);
-            }
-            SsArgs sa = SsArgs();
-            sa.M = M; sa.Mp = Mp;
-            const double *gd = d_gp_gen.p;
-            sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
-            sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
-            sa.c0 = ss_c0;
-            const int nw = (int)std::min<size_t>(npc, 4096);
-            d_gpark.alloc((size_t)nw * 64 * MS);
-            const dim3 grid(ceil_div(nw, 4)), block(256);
-            switch (NPL) {
+}
+
+void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
+    const hipStream_t sg = plan_stream(p.gamma);
+    const int nb2 = ceil_div((long long)Mp * Mp, 256);
+    GammaRowArgs ga;
+    ga.M = M; ga.Mp = Mp; ga.nrows = (int)n_e_rows; ga.perm = d_perme.p; ga.row_slab = d_erow_slab.p;
+    ga.slabs = d_slabs_eg.p; ga.g_eig = d_g_eig.p; ga.g_span = d_g_span.p; ga.dun = d_dun.p; ga.dsc = d_dsc.p; ga.dpow = d_dpow.p;
+    ga.Prm = d_Prm.p; ga.Pinvrm = d_Pinvrm.p; ga.PinvT = d_PinvT.p; ga.Sq = nullptr;
+    ga.alpha = d_alpha.p; ga.beta = d_beta.p; ga.gamma_rows = d_gamma_rows.p; ga.erow_desc = d_erow_desc.p;
+    switch (p.gamma_form) {
+    case StatsPlan::GAMMA_NONE: break;
+    case StatsPlan::GAMMA_PIECES: {
+        // long rows at 64 < M <= 256: eigen-power pieces + scan steps (chains_ss.hpp: k_piece_vectors)
+        build_gamma_pieces();
+        const int MS = 64 * NPL;
+        d_gp_gen.upload(ss_gen, sg);
+        d_gp_cs.alloc((size_t)Ke * 2 * Mp);
+        d_gp_l2d.alloc((size_t)Ke * Mp);
+        const size_t npc = gp_pieces.size();
+        d_gp_pvf.alloc(npc * Mp); d_gp_pvb.alloc(npc * Mp); d_gp_pgam.alloc(npc * Mp);
+        PieceArgs pa;
+        pa.M = M; pa.Mp = Mp; pa.npieces = (int)npc; pa.ntiles = (int)gp_tiles.size();
+        pa.pieces = d_gp_pieces.p; pa.tiles = d_gp_tiles.p; pa.Xs = d_Xs.p; pa.Ys = d_Ys.p; pa.dsc = d_dsc.p;
+        pa.PT = d_PT.p; pa.Pinvrm = d_Pinvrm.p; pa.cs = d_gp_cs.p; pa.l2d = d_gp_l2d.p; pa.pvf = d_gp_pvf.p; pa.pvb = d_gp_pvb.p; pa.pgam = d_gp_pgam.p;
+        hipLaunchKernelGGL(k_piece_rowsums, dim3(ceil_div(Ke * 2 * Mp, 256)), dim3(256), 0, sg, Ke, Mp, (const double *)d_PT.p,
+                           (const double *)d_Pinvrm.p, d_gp_cs.p, (const double *)d_dsc.p, d_gp_l2d.p);
+        if (pa.ntiles > 0) {
+            lds_limit_once<k_piece_vectors>();
+            const size_t shm = (size_t)4 * 16 * (Mp + 4) * sizeof(double);
+            const int nblk = std::min(2 * ceil_div(pa.ntiles, 4), 2048);
+            hipLaunchKernelGGL(k_piece_vectors, dim3(nblk), dim3(256), shm, sg, pa);
+        }
+        SsArgs sa = SsArgs();
+        sa.M = M; sa.Mp = Mp;
+        const double *gd = d_gp_gen.p;
+        sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
+        sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
+        sa.c0 = ss_c0;
+        const int nw = (int)std::min<size_t>(npc, 4096);
+        d_gpark.alloc((size_t)nw * 64 * MS);
+        const dim3 grid(ceil_div(nw, 4)), block(256);
+        switch (NPL) {
 #define GP_(x) case x: hipLaunchKernelGGL((k_gamma_rows_scan<x, true>), grid, block, 0, sg, sa, ga, (const RowInfo *)d_rowinfo.p, \
                                           (const double *)d_E.p, d_gpark.p, 64, nw, pa); break;
-                GP_(2) GP_(3)
-                default: GP_(4)
+            GP_(2) GP_(3)
+            default: GP_(4)
 #undef GP_
-            }
-            hipLaunchKernelGGL(k_gamma_merge_pieces, dim3((unsigned)ceil_div((long long)n_e_rows * Mp, 256)), dim3(256), 0, sg, Mp, (int)n_e_rows,
-                               (const int *)d_gp_pfirst.p, (const GPiece *)d_gp_pieces.p, (const double *)d_gp_pgam.p, d_gamma_rows.p);
-            gamma_pieces_last = true;
-        } else
-        if (eigfree) {
-            // no eigensystem on this path: 2 span - 1 scan steps per row, one (persistent) wavefront per row, the forward vectors parked
-            // as floats in the wavefront's piece of a scratch buffer
-            const int nw = (int)std::min<long long>((long long)n_e_rows, NPL >= 8 ? 1024 : 4096);
-            d_gpark.alloc((size_t)nw * ss_max_span * 64 * NPL);
-            const dim3 grid(ceil_div(nw, 4)), block(256);
-            switch (NPL) {
+        }
+        hipLaunchKernelGGL(k_gamma_merge_pieces, dim3((unsigned)ceil_div((long long)n_e_rows * Mp, 256)), dim3(256), 0, sg, Mp, (int)n_e_rows,
+                           (const int *)d_gp_pfirst.p, (const GPiece *)d_gp_pieces.p, (const double *)d_gp_pgam.p, d_gamma_rows.p);
+        break;
+    }
+    case StatsPlan::GAMMA_SCAN: {
+        // no eigensystem on this path: 2 span - 1 scan steps per row, one (persistent) wavefront per row, the forward vectors parked
+        // as floats in the wavefront's piece of a scratch buffer
+        const int nw = (int)std::min<long long>((long long)n_e_rows, NPL >= 8 ? 1024 : 4096);
+        d_gpark.alloc((size_t)nw * ss_max_span * 64 * NPL);
+        const dim3 grid(ceil_div(nw, 4)), block(256);
+        switch (NPL) {
 #define GS_(x) case x: hipLaunchKernelGGL((k_gamma_rows_scan<x>), grid, block, 0, sg, ss_args, ga, (const RowInfo *)d_rowinfo.p, \
                                           (const double *)d_E.p, d_gpark.p, ss_max_span, nw); break;
-                GS_(1) GS_(2) GS_(3) GS_(4) GS_(8)
-                default: GS_(16)
+            GS_(1) GS_(2) GS_(3) GS_(4) GS_(8)
+            default: GS_(16)
 #undef GS_
-            }
-        } else
-        if (!mfma_rows) {
-            d_Sq.alloc((size_t)G * Mp * Mp);
-            hipLaunchKernelGGL(k_span_q, dim3(nb2, G), dim3(256), 0, sg, M, Mp, G, (const int *)d_g_span.p,
-                               (const int *)d_g_eig.p, (const double *)d_dsc.p, (const double *)d_dpow.p, d_Sq.p);
-            ga.Sq = d_Sq.p;
         }
-        if (eigfree || gamma_pieces) {
-        } else if (mfma_rows) {
-            // one launch per (contig, eigen key): a workgroup shares one LDS copy of P, Pinv and the reciprocal eigenvalue differences
-            // (NT > 2: the reciprocal differences live in registers and the fold tile is half as wide - four wavefronts fit as well)
-            const int NW = 4;
-            const size_t shm2 = (size_t)((NT <= 2 ? 3 : 2) * Mp * (Mp + 1) + NW * (2 * 16 * (Mp + 1) + Mp * (NT <= 2 ? 17 : 9) + Mp) + Mp) * sizeof(double);
-            for (int ce = 0; ce < n_contigs * Ke; ++ce) {
-                const int q0 = ce_row_off[ce], q1 = ce_row_off[ce + 1];
-                if (q1 <= q0) continue;
-                const int nbatch = std::max(1, std::min(4, (q1 - q0 + 16 * NW * 2048 - 1) / (16 * NW * 2048)));   // batches of 16 rows per wavefront
-                const int nblk = ceil_div(q1 - q0, 16 * NW * nbatch);
-                switch (NT) {
-#define G_(x) case x: { static bool once = false; if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_gamma_rows_b<x>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; } \
-                        hipLaunchKernelGGL(k_gamma_rows_b<x>, dim3(nblk), dim3(256), shm2, sg, ga, q0, q1, ce % Ke, nbatch); } break;
-                    G_(1) G_(2) G_(3)
-                    default: G_(4)
-#undef G_
-                }
-            }
-        } else {
-            const size_t shm = (size_t)(3 * Mp + 256) * sizeof(double);
-            hipLaunchKernelGGL(k_gamma_rows_eig, dim3((unsigned)n_e_rows), dim3(256), shm, sg, ga);
-        }
-            if (gamma_side) { HIPCHK(hipEventRecord(ev[23], sg)); HIPCHK(hipStreamWaitEvent(s, ev[23], 0)); }
+        break;
     }
+    case StatsPlan::GAMMA_EIG_BATCHES: {
+        // one launch per (contig, eigen key): a workgroup shares one LDS copy of P, Pinv and the reciprocal eigenvalue differences
+        // (NT > 2: the reciprocal differences live in registers and the fold tile is half as wide - four wavefronts fit as well)
+        const int NW = 4;
+        const size_t shm2 = (size_t)((NT <= 2 ? 3 : 2) * Mp * (Mp + 1) + NW * (2 * 16 * (Mp + 1) + Mp * (NT <= 2 ? 17 : 9) + Mp) + Mp) * sizeof(double);
+        for (int ce = 0; ce < n_contigs * Ke; ++ce) {
+            const int q0 = ce_row_off[ce], q1 = ce_row_off[ce + 1];
+            if (q1 <= q0) continue;
+            const int nbatch = std::max(1, std::min(4, (q1 - q0 + 16 * NW * 2048 - 1) / (16 * NW * 2048)));   // batches of 16 rows per wavefront
+            const int nblk = ceil_div(q1 - q0, 16 * NW * nbatch);
+            switch (NT) {
+#define G_(x) case x: lds_limit_once<k_gamma_rows_b<x>>(); hipLaunchKernelGGL(k_gamma_rows_b<x>, dim3(nblk), dim3(256), shm2, sg, ga, q0, q1, ce % Ke, nbatch); break;
+                G_(1) G_(2) G_(3)
+                default: G_(4)
+#undef G_
+            }
+        }
+        break;
+    }
+    case StatsPlan::GAMMA_EIG_ROWS:
+        // (M > 64: the scalar kernel on a span-Q table in memory)
+        d_Sq.alloc((size_t)G * Mp * Mp);
+        hipLaunchKernelGGL(k_span_q, dim3(nb2, G), dim3(256), 0, sg, M, Mp, G, (const int *)d_g_span.p,
+                           (const int *)d_g_eig.p, (const double *)d_dsc.p, (const double *)d_dpow.p, d_Sq.p);
+        ga.Sq = d_Sq.p;
+        hipLaunchKernelGGL(k_gamma_rows_eig, dim3((unsigned)n_e_rows), dim3(256), (size_t)(3 * Mp + 256) * sizeof(double), sg, ga);
+        break;
+    }
+    if (p.gamma_beside) hand_over(EV_GAMMA_DONE, sg, stream);
+}
+
+bool smcpp_im::enqueue_stats(int signal_epoch) {
+    const StatsPlan &p = stats_plan = resolve_stats_plan();
+    const hipStream_t s = stream, sl = plan_stream(p.loglik);
+    if (h_ll_cap < n_contigs) {
+        if (h_ll) (void)hipHostFree(h_ll);
+        h_ll_cap = n_contigs;
+        HIPCHK(hipHostMalloc((void **)&h_ll, sizeof(double) * h_ll_cap, hipHostMallocCoherent | hipHostMallocMapped));
+        HIPCHK(hipHostGetDevicePointer((void **)&d_ll_view, h_ll, 0));
+    }
+    // the parameter arena of a lean E-step (Td, the emission table of a set_raw manager, the groups' log-scales) is copied on the
+    // second stream beside the chains (engine_params.hpp: arena_side); every stream of the statistics waits for it
+    if (arena_side) HIPCHK(hipStreamWaitEvent(s, ev[EV_ARENA], 0));
+    if (save_gamma) {
+        d_gamma_rows.alloc((size_t)total_rows * Mp);
+        // Every row 1 .. L of a contig is written whole by the statistics (span-1 rows: k_s1_scalars; span > 1 rows: the per-row gamma
+        // kernels); only row 0 (column 0 comes from gamma0) is nobody's: it alone is cleared.  (A memset of the whole buffer here,
+        // behind the fork event, could wipe rows the span-1 branch on its side stream had already written.)
+        for (int c = 0; c < n_contigs; ++c)
+            HIPCHK(hipMemsetAsync(d_gamma_rows.p + (size_t)contig_base[c] * Mp, 0, sizeof(double) * Mp, s));
+        if (p.gamma_beside) hand_over(EV_GAMMA_FORK, s, stream_hi);
+    }
+    // ---- fork ----
+    if (p.split) {
+        if (!ss_active) HIPCHK(hipEventRecord(ev[EV_STATS_FORK], s));
+        fork_from_chains(stream2);
+    }
+    // ---- log-likelihood (also materialises log_c per row) ----
+    LoglikArgs la;
+    la.cnorm = d_cnorm.p; la.rowinfo = d_rowinfo.p; la.g_logscale = d_g_logscale.p;
+    la.contig_base = d_contig_base.p; la.contig_L = d_contig_L.p; la.partial = d_llpart.p; la.loglik = d_loglik.p;
+    la.logc = d_logc.p; la.nblk = llblk;
+    la.loglik_host = d_ll_view;          // the final kernel writes the per-contig values into the pinned array as well: no copy
+    if (p.loglik == StatsPlan::THIRD) fork_from_chains(sl);
+    hipLaunchKernelGGL(k_loglik_partial, dim3(llblk, n_contigs), dim3(256), 0, sl, la);
+    hipLaunchKernelGGL(k_loglik_final, dim3(n_contigs), dim3(256), 0, sl, la);
+    if (p.loglik == StatsPlan::THIRD) HIPCHK(hipEventRecord(ev[EV_LOGLIK_DONE], sl));
+    FinArgs fa;
+    fa.M = M; fa.Mp = Mp; fa.K = K; fa.G = G; fa.Ke = Ke; fa.n_contigs = n_contigs;
+    fa.eb_slab_off = d_eb_slab_off.p; fa.eb_gid = d_eb_gid.p; fa.ce_bucket_off = d_ce_bucket_off.p;
+    fa.s1_slab_off = d_s1_slab_off.p; fa.gk_slab_off = d_gk_slab_off.p; fa.g_span = d_g_span.p;
+    fa.e_kid = d_e_kid.p; fa.dsc = d_dsc.p; fa.dun = d_dun.p; fa.Prm = d_Prm.p; fa.Pinvrm = d_Pinvrm.p;
+    fa.E = d_E.p; fa.Td = d_Td.p; fa.ZS = ZS; fa.red_e = nullptr; fa.red_1 = d_red_1.p; fa.red_g = d_red_g.p; fa.ZG = p.s1_one_pass ? ZG : 1;
+    fa.alpha = d_alpha.p; fa.beta = d_beta.p; fa.contig_base = d_contig_base.p;
+    fa.Z = d_Z.p; fa.Y = d_Y.p; fa.xisum = d_xisum.p; fa.gsum = d_gsum.p; fa.gamma0 = d_gamma0.p;
+    fa.dpow = d_dpow.p;
+    fa.part_e = nullptr;
+    fa.eigfree = eigfree ? 1 : 0;
+    if (!slabs_eg.empty() && p.eigen != StatsPlan::EIG_GEN2) {
+        d_part_e.alloc(std::max<size_t>(1, p.teams_span_gt1 ? teams_eg.size() : slabs_eg.size()) * Mp * Mp);
+        fa.part_e = d_part_e.p;
+        if (eigfree) { d_red_e.alloc(std::max<size_t>(1, eb_gid.size()) * Mp * Mp); fa.red_e = d_red_e.p; }
+    }
+    // ---- the two branches ----
+    if (p.rank_early) {
+        launch_span_gt1_rank(p);
+        if (p.span1 == StatsPlan::MAIN) HIPCHK(hipEventRecord(ev[EV_RANK2_DONE], plan_stream(p.span_gt1)));
+    }
+    launch_span1_branch(p);
+    launch_span_gt1_branch(p, fa);
+    if (p.gsum_at == StatsPlan::GSUM_SPAN_GT1_TAIL) {
+        HIPCHK(hipStreamWaitEvent(plan_stream(p.span_gt1), ev[EV_S1_SCALARS], 0));
+        sum_parts(d_gpart.p, d_gk_slab_off.p, d_red_g.p, Mp, n_contigs * K, 1, plan_stream(p.span_gt1));
+    }
+    // ---- joins: the main stream waits for ONE event of the second stream (every wait is a barrier packet of a few microseconds on
+    // the queue it is put on, signalled or not); the third stream joins through the second where that carries the span-1 branch ----
+    if (p.split) {
+        if (p.loglik == StatsPlan::THIRD && p.span1 == StatsPlan::SECOND) HIPCHK(hipStreamWaitEvent(stream2, ev[EV_LOGLIK_DONE], 0));
+        hand_over(EV_SIDE_DONE, stream2, s);
+    }
+    if (p.gsum_at == StatsPlan::GSUM_OWN_STREAM) HIPCHK(hipStreamWaitEvent(s, ev[EV_GSUM_DONE], 0));
+    // ---- finalisation ----
+    const int nb2 = ceil_div((long long)Mp * Mp, 256), nbf = fin_blocks(Mp, K);
+    const bool signals = signal_epoch != 0 && p.fin_signals;
+    if (signals) {
+        if (!d_fin_ctr.p) { d_fin_ctr.alloc(1); HIPCHK(hipMemsetAsync(d_fin_ctr.p, 0, sizeof(unsigned), s)); fin_target = 0; }
+        fin_target += (unsigned)nbf * (unsigned)n_contigs;
+    }
+    hipLaunchKernelGGL(k_fin_both, dim3(nbf, n_contigs), dim3(256), 0, s, fa, nb2, d_fin_ctr.p, fin_target,
+                       signals ? d_done_view : (int *)nullptr, signal_epoch);
+    // ---- per-row gammas ----
+    launch_gamma_rows(p);
     HIPCHK(hipGetLastError());
-    if (ll_own) HIPCHK(hipStreamWaitEvent(s, ev[19], 0));
-    HIPCHK(hipEventRecord(ev[5], s));
+    if (p.loglik == StatsPlan::THIRD && p.span1 == StatsPlan::MAIN) HIPCHK(hipStreamWaitEvent(s, ev[EV_LOGLIK_DONE], 0));
+    HIPCHK(hipEventRecord(ev[EV_STATS_DONE], s));
     stats_enqueued = true;
+    return signals;
 }
 
 // The pieces of the eigen rows (chains_ss.hpp: k_piece_vectors): at most 64 positions each, in the order of the sorted eigen-row
@@ -1302,33 +1242,33 @@ void smcpp_im::resolve_timing() {
     if (!timing_pending) return;
     timing_pending = false;
     HIPCHK(hipSetDevice(device));
-    (void)hipEventSynchronize(ev[5]);
+    (void)hipEventSynchronize(ev[EV_STATS_DONE]);
     float f_ms = 0, b_ms = 0, s_ms = 0, fin_ms = 0;
     if (ss_active) {
         // one launch per pass for both directions, timed below
     } else if (chains_dual) {
-        (void)hipEventElapsedTime(&f_ms, ev[1], ev[7]);   // forward passes (main stream)
-        (void)hipEventElapsedTime(&b_ms, ev[2], ev[3]);   // backward passes (second stream), overlapping the forward ones
+        (void)hipEventElapsedTime(&f_ms, ev[EV_CHAINS_START], ev[EV_FWD_END]);   // forward passes (main stream)
+        (void)hipEventElapsedTime(&b_ms, ev[EV_BWD_START], ev[EV_CHAINS_END]);   // backward passes (second stream), overlapping the forward ones
     } else {
-        (void)hipEventElapsedTime(&f_ms, ev[1], ev[2]);
-        (void)hipEventElapsedTime(&b_ms, ev[2], ev[3]);
+        (void)hipEventElapsedTime(&f_ms, ev[EV_CHAINS_START], ev[EV_BWD_START]);
+        (void)hipEventElapsedTime(&b_ms, ev[EV_BWD_START], ev[EV_CHAINS_END]);
     }
     float chains_ms = 0;
     if (ss_active) {
-        // every pass of both directions between two events: ev[10] in front of the first launch, ev[3] behind the last one (a rare
-        // round that needs more passes than were launched up front includes the host's look at the flags)
-        (void)hipEventElapsedTime(&chains_ms, ev[10], ev[3]);
+        // every pass of both directions between two events: EV_FIRST_PASS in front of the first launch, EV_CHAINS_END behind the last
+        // one (a rare round that needs more passes than were launched up front includes the host's look at the flags)
+        (void)hipEventElapsedTime(&chains_ms, ev[EV_FIRST_PASS], ev[EV_CHAINS_END]);
         f_ms = b_ms = chains_ms;
-    } else (void)hipEventElapsedTime(&chains_ms, ev[1], ev[3]);
+    } else (void)hipEventElapsedTime(&chains_ms, ev[EV_CHAINS_START], ev[EV_CHAINS_END]);
     if (prepass_launched) {
-        // pass 0 ran before ev[1] (concurrently with the host eigensolve): add its kernel intervals
-        (void)hipEventElapsedTime(&pre_f_ms, ev[10], ev[11]);
-        (void)hipEventElapsedTime(&pre_b_ms, ev[12], ev[13]);
+        // pass 0 ran before EV_CHAINS_START (concurrently with the host eigensolve): add its kernel intervals
+        (void)hipEventElapsedTime(&pre_f_ms, ev[EV_FIRST_PASS], ev[EV_PRE_FWD_END]);
+        (void)hipEventElapsedTime(&pre_b_ms, ev[EV_PRE_BWD_START], ev[EV_PRE_BWD_END]);
         f_ms += pre_f_ms; b_ms += pre_b_ms;
         chains_ms += std::max(pre_f_ms, pre_b_ms);
     }
-    (void)hipEventElapsedTime(&s_ms, ev[3], ev[4]);
-    (void)hipEventElapsedTime(&fin_ms, ev[4], ev[5]);
+    (void)hipEventElapsedTime(&s_ms, ev[EV_CHAINS_END], ev[EV_SPAN1_DONE]);
+    (void)hipEventElapsedTime(&fin_ms, ev[EV_SPAN1_DONE], ev[EV_STATS_DONE]);
     (void)hipGetLastError();      // an interval over an event this E-step never recorded must not surface in the next launch check
     timing[0] = t_host01;
     timing[1] = chains_ms;   // wall time of both chains (they overlap in dual-stream mode)
@@ -1357,7 +1297,7 @@ void smcpp_im::estep() {
         d_gamma_rows.alloc((size_t)total_rows * Mp);
         HIPCHK(hipMemsetAsync(d_gamma_rows.p, 0xff, sizeof(double) * d_gamma_rows.n, stream));
     }
-    HIPCHK(hipEventRecord(ev[0], stream));
+    HIPCHK(hipEventRecord(ev[EV_ESTEP], stream));
     // span > 1 rows without an eigensystem (kernels.hpp: k_span_fold): the span is expanded by smax steps of two M x M products
     const bool eigfree_off = opt().off(smcpp_opt::O_EIGFREE);
     // (round 6) save_gamma keeps the eigen-free path: the per-row posteriors of the span > 1 rows come from scan steps as well
@@ -1403,8 +1343,8 @@ void smcpp_im::estep() {
         }
     }
     auto t2 = std::chrono::steady_clock::now();
-    // the event intervals are read when somebody asks for them (smcpp_last_timing, the debug log): ev[5] sits BEHIND the completion
-    // word the host has just seen, so querying it here would mean waiting for it
+    // the event intervals are read when somebody asks for them (smcpp_last_timing, the debug log): EV_STATS_DONE sits BEHIND the
+    // completion word the host has just seen, so querying it here would mean waiting for it
     t_host01 = std::chrono::duration<double, std::milli>(t1 - t0).count();
     t_host12 = std::chrono::duration<double, std::milli>(t2 - t1).count();
     host_timing[3] = t_host01;

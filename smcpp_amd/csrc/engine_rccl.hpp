@@ -201,8 +201,8 @@ int smcpp_chain_mode(smcpp_im *im) { return im ? (im->ss_static ? (im->ss_hybrid
 void smcpp_reload_options(void) { smcpp_opt::reload(); }
 
 // One JSON object: the switches found in the environment and the plan this manager resolved from them and from its input (chain
-// family, states per lane, chunk counts, history passes, arithmetic of the stored passes of the LAST E-step).  Returns the length
-// the text needs (without the terminating zero); writes at most cap - 1 characters.
+// family, states per lane, chunk counts, history passes, arithmetic of the stored passes and the statistics plan of the LAST
+// E-step).  Returns the length the text needs (without the terminating zero); writes at most cap - 1 characters.
 int smcpp_describe(smcpp_im *im, char *buf, int cap) {
     std::string s = "{";
     s += smcpp_opt::describe_options();
@@ -221,9 +221,23 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
                  im->chunks_b.size(), im->ss_wpc, (im->ss_static && im->ss_args.halo) ? "true" : "false", im->ss_light_f, im->ss_light_b,
                  (im->ss_static && im->ss_args.mixed) ? "true" : "false", im->last_ss_passes, im->ss_launched,
                  (opt().on(smcpp_opt::O_SS_CERT_PASS) || im->ss_need_cert_pass) ? "true" : "false", im->save_gamma ? "true" : "false",
-                 im->eigfree ? "true" : "false", !im->save_gamma ? "none" : im->eigfree ? "scan steps" : im->gamma_pieces_last ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
+                 im->eigfree ? "true" : "false", !im->save_gamma ? "none" : im->eigfree ? "scan steps" : im->stats_plan.gamma_form == StatsPlan::GAMMA_PIECES ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
                  im->warm_start ? "true" : "false", omp_get_max_threads());
         s += t;
+        // the statistics plan of the last E-step (null before the first one): the stream of every branch, the form of every kernel family
+        const StatsPlan &p = im->stats_plan;
+        static const char *const stream[] = {"main", "second", "third", "high priority"}, *const rank[] = {"per slab", "teams", "wide"};
+        static const char *const eigen[] = {"none", "fold on the scans", "fold on the matrix cores", "generation 2", "classic"};
+        static const char *const gsum[] = {"one pass", "own stream", "span > 1 tail", "span-1 branch"};
+        static const char *const gamma[] = {"none", "scan steps", "eigen-power pieces + scan steps", "eigensystem batches", "eigensystem rows"};
+        snprintf(t, sizeof t,
+                 ", \"statistics\": {\"span_gt1_stream\": \"%s\", \"span1_stream\": \"%s\", \"gamma_sums_stream\": \"%s\", "
+                 "\"loglik_stream\": \"%s\", \"per_row_gamma_stream\": \"%s\", \"span1_form\": \"%s\", \"rank_update\": \"%s\", "
+                 "\"eigen\": \"%s\", \"span_gt1_rank_early\": %s, \"gamma_sums_reduced\": \"%s\", \"per_row_gamma\": \"%s\", "
+                 "\"per_row_gamma_beside\": %s}",
+                 stream[p.span_gt1], stream[p.span1], stream[p.gsum], stream[p.loglik], stream[p.gamma], p.s1_one_pass ? "one pass" : "two kernels",
+                 rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false");
+        s += p.resolved ? t : ", \"statistics\": null";
     }
     s += "}";
     if (buf && cap > 0) {

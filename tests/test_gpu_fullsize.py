@@ -54,6 +54,13 @@ def _onepop(params, contigs, n, route="raw"):
 ROUTES = pytest.mark.parametrize("route", ["raw", "params"])
 
 
+def _check_stats_plan(im, **want):
+    """The arrangement of the statistics phase the E-step ran (describe()["statistics"]): what the size rules pick for this input."""
+    got = im.describe()["statistics"]
+    assert got == dict(dict(loglik_stream="third", rank_update="teams", eigen="fold on the scans", per_row_gamma="none",
+                            per_row_gamma_stream="main", per_row_gamma_beside=False), **want), got
+
+
 @pytest.mark.parametrize("name,params,n", [("headline", "params_M64_n20.npz", 20), ("c2", "params_M32_n10.npz", 10)])
 def test_full_100mbp_contig_vs_compiled_reference(name, params, n):
     from smcpp_amd import synth
@@ -69,6 +76,10 @@ def test_full_100mbp_contig_vs_compiled_reference(name, params, n):
     _check_stats(im, 0, g, g["xisum"], g["gs"], g["gs_have"], g["gamma0"])
     q = np.array(im.Q(separate=True))
     assert np.all(np.abs(q - g["q"][0]) <= STAT_TOL * np.abs(g["q"][0])), (q, g["q"][0])
+    if name == "headline":
+        # eigen-free, M <= 64, fewer than 10^6 span > 1 rows: that branch keeps the main stream and its rank update goes first
+        _check_stats_plan(im, span_gt1_stream="main", span1_stream="second", gamma_sums_stream="second", span1_form="one pass",
+                          span_gt1_rank_early=True, gamma_sums_reduced="one pass")
 
 
 def test_headline_weak_scaling_contigs_vs_compiled_reference():
@@ -115,6 +126,9 @@ def test_whole_genome_22_contigs_vs_compiled_reference(route):
     q = np.array(im.Q(separate=True))
     qr = g["q"].sum(axis=0)
     assert np.all(np.abs(q - qr) <= STAT_TOL * np.abs(qr)), (q, qr)
+    # millions of span-1 rows: the one-pass span-1 form; millions of span > 1 rows: the two rank updates side by side
+    _check_stats_plan(im, span_gt1_stream="second", span1_stream="main", gamma_sums_stream="main", span1_form="one pass",
+                      span_gt1_rank_early=False, gamma_sums_reduced="one pass")
 
 
 @ROUTES
@@ -177,3 +191,6 @@ def test_c5_whole_contig_vs_compiled_reference(route):
     _check_stats(im, 0, g, g["xisum"], g["gs"], g["gs_have"], g["gamma0"])
     q = np.array(im.Q(separate=True))
     assert np.all(np.abs(q - g["q"]) <= STAT_TOL * np.abs(g["q"])), (q, g["q"])
+    # M = 256: the wide rank updates, the span > 1 branch on the second stream, the span-1 gamma sums reduced at its tail
+    _check_stats_plan(im, span_gt1_stream="second", span1_stream="main", gamma_sums_stream="main", span1_form="two kernels",
+                      rank_update="wide", span_gt1_rank_early=True, gamma_sums_reduced="span > 1 tail")

@@ -275,6 +275,13 @@ def run_case(case, engine_opt):
     print(f"{case}: plan {got}")
     for k, v in want.items():
         assert plan[k] == v, (case, k, plan[k], v, plan)
+    # the statistics plan: the per-row form, and whether it runs beside the statistics (all but the eigen-power pieces, which read
+    # the statistics' own products, unless SMCPP_GAMMA_SIDE=0)
+    st = im.describe()["statistics"]
+    form = {SCAN: SCAN, PIECES: PIECES, EIG: "eigensystem batches" if M <= 64 else "eigensystem rows"}[want["per_row_gamma"]]
+    beside = want["per_row_gamma"] != PIECES and switches.get("SMCPP_GAMMA_SIDE") != "0"
+    assert (st["per_row_gamma"], st["per_row_gamma_beside"], st["per_row_gamma_stream"]) == \
+        (form, beside, "high priority" if beside else "main"), (case, st)
     return im, contigs
 
 
