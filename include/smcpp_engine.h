@@ -177,6 +177,13 @@ int smcpp_last_timing(smcpp_im *im, double out[9]);
  * this is the engine's own decomposition, exported for the CPU tests). */
 int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *rows, long long nslots, long long floor_cost, int *out);
 int smcpp_chain_mode(smcpp_im *im);
+/* diagnostics (host only): the chunk list of the scan chains as the last plan cut it - backward == 0: the forward chain's, else the
+ * backward chain's (the two directions have lists of their own).  Writes up to `cap` chunks into out[5 * cap] as (contig, r0, r1, h0,
+ * h1) and returns how many there are (call with cap = 0 to size the buffer); -1 on a NULL manager.  The chunk owns rows r0+1 .. r1 of
+ * its contig, 1-based; a forward chunk enters through rows h0+1 .. h1 in float and h1+1 .. r0 in fp64 of its neighbour (h0 <= h1 <= r0),
+ * a backward one through rows h0 .. h1+1 in float and h1 .. r1+1 in fp64 (h0 >= h1 >= r1); h0 == h1 == r0 (r1): no halo.  Rows are
+ * the engine's own: where long rows are cut (plan "long_rows_cut") a caller's row of span s is ceil(s / 64) consecutive rows. */
+int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out);
 /* Every SMCPP_* environment switch of the engine is parsed ONCE per process (smcpp_amd/csrc/engine_options.hpp holds the one
  * table of them); smcpp_reload_options re-reads the environment (tests; never while an E-step runs).  smcpp_describe writes one
  * JSON object - the switches that are set and the plan `im` resolved (chain family, chunk counts, history passes, whether the

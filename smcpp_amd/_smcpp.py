@@ -252,6 +252,15 @@ class _PyInferenceManager:
         5 scans over the semiseparable structure of the transition matrix (the other families are its fallback)."""
         return int(E.lib().smcpp_chain_mode(self._im))
 
+    def chunks(self, backward=False):
+        """The scan chains' chunk list of one direction as the current plan cut it (`smcpp_debug_chunks`): an int array [n, 5] of
+        (contig, r0, r1, h0, h1); the chunk owns the engine's rows r0+1 .. r1, h0 / h1 bound the halo it enters through."""
+        n = int(E.lib().smcpp_debug_chunks(self._im, int(bool(backward)), 0, None))
+        out = np.zeros((max(n, 0), 5), dtype=np.int32)
+        if n > 0:
+            E.lib().smcpp_debug_chunks(self._im, int(bool(backward)), n, E.iptr(out))
+        return out
+
     def describe(self):
         """The engine's environment switches and the plan this manager resolved (chain family, chunks, history passes, whether the
         stored passes of the last E-step ran their scans in float): `smcpp_describe`."""

@@ -79,6 +79,7 @@ cdef extern from "smcpp_engine.h":
     int smcpp_last_timing(smcpp_im *im, double *out) nogil
     int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *rows, long long nslots, long long floor_cost, int *out) nogil
     int smcpp_chain_mode(smcpp_im *im) nogil
+    int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out) nogil
     void smcpp_reload_options() nogil
     int smcpp_describe(smcpp_im *im, char *buf, int cap) nogil
     int smcpp_debug_ss_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b) nogil

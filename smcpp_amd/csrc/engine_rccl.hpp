@@ -197,6 +197,18 @@ int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *row
 
 int smcpp_chain_mode(smcpp_im *im) { return im ? (im->ss_static ? (im->ss_hybrid ? 6 : 5) : im->chain_mode) : -1; }
 
+// Test hook (tests/test_gpu_seams.py): the chunk list of one direction as make_chunks left it, (contig, r0, r1, h0, h1) per chunk.
+int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out) {
+    if (!im) return -1;
+    const std::vector<Chunk> &v = backward ? im->chunks_b : im->chunks;
+    for (size_t j = 0; j < v.size() && (long long)j < (long long)cap && out; ++j) {
+        const Chunk &ch = v[j];
+        const int t[5] = {ch.contig, ch.r0, ch.r1, ch.h0, ch.h1};
+        std::copy(t, t + 5, out + 5 * j);
+    }
+    return (int)v.size();
+}
+
 // Every SMCPP_* switch is parsed once per process (engine_options.hpp); this re-reads the environment.
 void smcpp_reload_options(void) { smcpp_opt::reload(); }
 
