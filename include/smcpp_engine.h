@@ -187,7 +187,8 @@ int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out);
 /* Every SMCPP_* environment switch of the engine is parsed ONCE per process (smcpp_amd/csrc/engine_options.hpp holds the one
  * table of them); smcpp_reload_options re-reads the environment (tests; never while an E-step runs).  smcpp_describe writes one
  * JSON object - the switches that are set and the plan `im` resolved (chain family, chunk counts, history passes, whether the
- * stored passes of the last E-step ran their scans in float) - and returns the length it needs; `im` may be NULL. */
+ * stored passes of the last E-step ran their scans in float; "q_route": whether the last smcpp_q was evaluated by the device
+ * kernels, "device", by the host loops, "host", or not yet, "none") - and returns the length it needs; `im` may be NULL. */
 void smcpp_reload_options(void);
 int smcpp_describe(smcpp_im *im, char *buf, int cap);
 /* Test hook of family 5: one position of both scan chains on nvec vectors: out_f = e o (T^T x), out_b = T (e o x); T is

@@ -164,7 +164,9 @@ int smcpp_q(smcpp_im *im, double val[4], double *jac) {
     API_BEGIN
     const int M = im->M, K = im->K;
     if (!im->have_raw) im->prepare_params();   // Q() does do_dirty_work() first (inference_manager.cpp:119)
-    if (im->q_device(val, jac)) return 0;
+    im->q_route = smcpp_im::Q_ROUTE_NONE;
+    if (im->q_device(val, jac)) { im->q_route = smcpp_im::Q_ROUTE_DEVICE; return 0; }
+    im->q_route = smcpp_im::Q_ROUTE_HOST;
     im->sync_host_E();
     im->ensure_dT();
     if ((int)im->pi.size() != M) throw std::runtime_error("parameters are not set");

@@ -147,6 +147,8 @@ struct smcpp_im {
     };
     std::unique_ptr<QDev> qdev;
     bool q_device(double val[4], double *jac);
+    enum { Q_ROUTE_NONE = 0, Q_ROUTE_DEVICE, Q_ROUTE_HOST };
+    int q_route = Q_ROUTE_NONE;            // who evaluated the last smcpp_q (smcpp_describe: "q_route")
     void ensure_dT();
     bool ss_static = false;                // the input qualifies (short spans); whether T does is decided on every E-step
     // hybrid scan chains (un-binned data): rows whose span exceeds ss_hyb_th take ONE eigen-power step inside the scan kernel

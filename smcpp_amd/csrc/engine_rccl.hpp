@@ -250,6 +250,9 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
                  stream[p.span_gt1], stream[p.span1], stream[p.gsum], stream[p.loglik], stream[p.gamma], p.s1_one_pass ? "one pass" : "two kernels",
                  rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false");
         s += p.resolved ? t : ", \"statistics\": null";
+        // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
+        static const char *const route[] = {"none", "device", "host"};
+        s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";
     }
     s += "}";
     if (buf && cap > 0) {

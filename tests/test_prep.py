@@ -287,27 +287,86 @@ def test_device_preparation_phases_equal_host_preparation(fixture, nder):
     np.testing.assert_allclose(o["dT"], dT, rtol=1e-9, atol=1e-16 * sc)
 
 
-@pytest.mark.parametrize("fixture,nder", [("params_M32_n10.npz", 3), ("params_M64_n20.npz", 5)])
-def test_device_q_phases_equal_dense_evaluation(fixture, nder):
+def _q_sweep_params():
+    import qref
+    return [pytest.param(("params_M32_n10.npz", 3), id="params_M32_n10.npz-3"), pytest.param(("params_M64_n20.npz", 5), id="params_M64_n20.npz-5")] + \
+           [pytest.param(c, id=qref.sweep_id(c)) for c in qref.SWEEP] + [pytest.param("floors", id="floors")]
+
+
+@pytest.mark.parametrize("case", _q_sweep_params())
+def test_device_q_phases_equal_dense_evaluation(case):
     """Q and its gradient as the device kernel forms them (transition matrix and its Jacobian from the O(M) generator planes,
-    never materialised) against the plain dense evaluation sum w log x / sum (w / x) dx on the host preparation's pi, T, E and
-    Jacobians."""
+    never materialised; `_engine.dev_q_emulate`: the kernels' __host__ __device__ phases run serially) against the plain dense
+    evaluation sum w log x / sum (w / x) dx on the host preparation's pi, T, E and Jacobians in extended precision (tests/qref.py),
+    on two reference fixtures and over the shape sweep of tests/test_gpu_qgrad.py: M != Mp, tail groups of the four-direction
+    scalar, more directions than pieces, M up to 1024 (a second serially), the last sample size the device preparation supports;
+    the first one it refuses (n = 56) must raise instead of evaluating."""
     import os
+    import qref
     from smcpp_amd import _engine
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", fixture))
-    n = int(g["n"]); keys = g["keys"]; M = len(g["hs"]) - 1
-    args = (n, g["hs"], float(g["pol"]), g["a"], g["s"], float(g["theta"]), float(g["rho"]), float(g["alpha"]), keys)
-    rng = np.random.default_rng(9)
-    da = rng.standard_normal((len(g["a"]), nder))
-    pi, T, E, dpi, dT, dE = _engine.host_prep_onepop_jac(args[0], args[1], args[2], args[3], da, *args[4:])
-    g0 = rng.random(M); xi = rng.random((M, M)) * np.exp(-np.abs(np.subtract.outer(np.arange(M), np.arange(M))))
-    gs = rng.random((len(keys), M)) * 100.0
-    gs[3] = 0.0                                                      # a key no contig holds
-    val, jac = _engine.dev_q_emulate(args[0], args[1], args[2], args[3], da, *args[4:], g0, xi, gs)
-    nb = keys[:, 2] > 0
-    ref = np.array([np.sum(g0 * np.log(pi)), np.sum(gs[~nb] * np.log(E[~nb])), np.sum(gs[nb] * np.log(E[nb])), np.sum(xi * np.log(T))])
-    rj = np.array([np.einsum("i,id->d", g0 / pi, dpi), np.einsum("km,kmd->d", gs[~nb] / E[~nb], dE[~nb]),
-                   np.einsum("km,kmd->d", gs[nb] / E[nb], dE[nb]), np.einsum("ij,ijd->d", xi / T, dT)])
-    np.testing.assert_allclose(val, ref, rtol=1e-12)
-    for t in range(4):
-        assert np.max(np.abs(jac[t] - rj[t])) <= 1e-11 * np.abs(rj[t]).max(), t
+    p, floors = None, case == "floors"
+    if isinstance(case, tuple) and isinstance(case[0], str):
+        fixture, nder = case
+        g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", fixture))
+        n = int(g["n"]); keys = g["keys"]; M = len(g["hs"]) - 1
+        rng = np.random.default_rng(9)
+        da = rng.standard_normal((len(g["a"]), nder))
+        head = (n, g["hs"], float(g["pol"]), g["a"], da, g["s"], float(g["theta"]), float(g["rho"]), float(g["alpha"]), keys)
+    else:
+        if floors:                                  # (entries of T, E and pi on their floors: tests/qref.py::floor_inputs)
+            case, p = qref.floor_inputs()
+        else:
+            p = qref.sweep_inputs(case)
+        n = p["n"]; keys = qref.edge_keys(n); M = len(p["hs"]) - 1
+        rng = np.random.default_rng(9)
+        head = (n, p["hs"], p["pol"], p["a"], p["da"], p["s"], p["theta"], p["rho"], p["alpha"], keys)
+    g0, xi, gs = qref.synthetic_statistics(rng, M, len(keys))
+    if n == 56:
+        with pytest.raises(RuntimeError, match="does not support this sample size"):
+            _engine.dev_q_emulate(*head, g0, xi, gs)
+        return
+    val, jac = _engine.dev_q_emulate(*head, g0, xi, gs)
+    ref, rj, prep = qref.host_reference(*head, g0, xi, gs)
+    if floors:
+        zT, zE = qref.floored_entries(prep)
+        assert zT.mean() >= 0.01 and zE.sum() >= 1
+    ev, ej = qref.errors(val, jac, ref, rj)
+    print(case, "emulated device phases vs dense longdouble: values", ev, "Jacobian rows", ej)
+    assert np.all(np.isfinite(val)) and np.all(np.isfinite(jac))
+    assert ev <= 1e-12
+    assert ej <= 1e-11
+    if p is not None:
+        qref.check_marked_columns(case, jac)
+        if M > 2:
+            assert np.abs(np.asarray(rj, dtype=float)).max() > 1.0
+
+
+@pytest.mark.parametrize("M,n", [(17, 7), (256, 50)])
+def test_host_q_gradient_matches_richardson_differences(M, n):
+    """A reference for the dense reference, free of dual numbers: dQ along three dense random directions by Richardson-extrapolated
+    central differences (4 D(h) - D(2 h)) / 3 of the longdouble dense Q over the host preparation's VALUES (tests/qref.py),
+    statistics held fixed, against the same dense formula on `host_prep_onepop_jac`'s duals.  Bar: what
+    test_q_gradient_matches_finite_differences holds finite differences to, 1e-4 relative + 1e-5 absolute (h = 1e-3 in units of the
+    direction: truncation h^4, rounding eps |Q| / h, both orders below the bar).  A finite difference across a floor's kink is no
+    reference, so the keys are those whose emission vector stays a decade above the 1e-10 floor (and is not the constant 1 of a
+    fully missing observation); that no entry of pi, T or E has an all-zero derivative row is asserted, not assumed."""
+    import qref
+    from smcpp_amd import _engine
+    p = qref.sweep_inputs((M, n, 1, 16, 3), seed=77)
+    keys = qref.edge_keys(n)
+    head = lambda kk: (n, p["hs"], p["pol"], p["a"], p["da"], p["s"], p["theta"], p["rho"], p["alpha"], kk)       # noqa: E731
+    E0 = _engine.host_prep_onepop(n, p["hs"], p["pol"], p["a"], p["s"], p["theta"], p["rho"], p["alpha"], keys)[2]
+    keys = np.ascontiguousarray(keys[(E0.min(axis=1) > 1e-9) & (E0.max(axis=1) < 1.0)])
+    assert len(keys) >= n                                             # (most of the key list survives)
+    rng = np.random.default_rng(13)
+    g0, xi, gs = qref.synthetic_statistics(rng, M, len(keys))
+    _, jac, prep = qref.host_reference(*head(keys), g0, xi, gs)
+    for name, d in (("pi", prep[3]), ("T", prep[4]), ("E", prep[5])):
+        assert not np.any(np.all(d == 0, axis=-1)), f"an entry of {name} sits on a floor (all-zero derivative row)"
+    fd = qref.richardson(*head(keys), g0, xi, gs)
+    jac = np.asarray(jac, dtype=float); fd = np.asarray(fd, dtype=float)
+    err = np.abs(fd - jac)
+    print((M, n), "keys", len(keys), "Richardson vs duals: worst |diff| / (1e-4 |jac| + 1e-5) =", float(np.max(err / (1e-4 * np.abs(jac) + 1e-5))),
+          "worst relative", float(np.max(err / np.abs(jac))))
+    assert np.all(err <= 1e-4 * np.abs(jac) + 1e-5), (fd, jac)
+    assert np.abs(jac).min(axis=1).max() > 1.0
