@@ -320,6 +320,33 @@ int smcpp_host_prep_twopop(int n1, int n2, int a1, int a2, int n_hs, const doubl
                            int K2, const double *pa2, const double *ps2, double split, double theta, double rho,
                            double alpha, int K, const int *keys, double *pi, double *T, double *E);
 
+/* ---- posterior products on the device (no reference counterpart; smcpp_amd/csrc/posterior_dev.hpp) ------------------- */
+
+/* Products of the per-row posteriors of the LAST E-step, which must have run with save_gamma, computed by kernels that read the rows
+ * where they lie.  Contig `contig` has L caller's rows with spans s_1 .. s_L; gamma is the [M x (L + 1)] matrix smcpp_get_gamma
+ * returns and p[:, l] = gamma[:, l] / sum_m gamma[m, l].  A column selection is range(start, stop, step) over 0 .. L, of
+ * ncols = ceil((stop - start) / step) columns.  All pointers are host pointers; output pointers that are NULL are skipped.  Each
+ * call fails before anything is launched when no E-step has run, the last one ran without save_gamma, the contig index is out of
+ * range, start < 0, stop > L + 1, start >= stop, step < 1, window_bp < 1, nq outside 0 .. 8, a level outside (0, 1), or a weight
+ * that is not finite.
+ *
+ * smcpp_posterior_columns: out [M x ncols] row-major, doubles or (f32 != 0) floats: p if normalize != 0, else gamma (a copy:
+ * bit for bit what smcpp_get_gamma returns); colsum [ncols] the column sums (states added in ascending order). */
+int smcpp_posterior_columns(smcpp_im *im, int contig, long long start, long long stop, long long step,
+                            int normalize, int f32, void *out, double *colsum /* may be NULL */);
+/* smcpp_posterior_summary: per selected column, without forming the matrix: colsum, argmax (the first maximum, as
+ * smcpp_get_gamma_argmax), mean = sum_m weights[m] p[m, l] (skipped when weights is NULL), and for each of the nq levels q[k]
+ * qstate[k x ncols] = min{m : sum_{i <= m} p[i, l] >= q[k]} (running sum in ascending order). */
+int smcpp_posterior_summary(smcpp_im *im, int contig, long long start, long long stop, long long step,
+                            const double *weights /* [M] or NULL */, int nq, const double *q,
+                            double *colsum, int *argmax, double *mean, int *qstate /* [nq x ncols] */);
+/* smcpp_posterior_windows: the average of p over windows of window_bp base pairs.  With P_l = s_1 + .. + s_l row l >= 1 covers
+ * base pairs [P_{l-1}, P_l); window w covers [w W, min((w + 1) W, P_L)); out[:, w] = sum_l overlap(l, w) p[:, l] / (base pairs of
+ * the window that are covered), rows added in ascending order.  Column 0 of gamma takes no part.  *n_windows = ceil(P_L / W);
+ * out [M x n_windows] row-major. */
+int smcpp_posterior_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
+                            double *out /* [M x n_windows]; NULL: only n_windows is written */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,54 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_get_gamma_argmax(self._im, c, E.iptr(out)))
         return out
 
+    # ---- posterior products computed on the device (include/smcpp_engine.h: smcpp_posterior_*; no counterpart in _smcpp.pyx) ----
+    def _selection(self, c, start, stop, step):
+        c = int(c)
+        if stop is None:
+            stop = int(self._Ls[c]) + 1 if 0 <= c < self._num_hmms else 1   # (a bad contig index: the engine raises)
+        start, stop, step = int(start), int(stop), int(step)
+        ncols = max(0, -(-(stop - start) // step)) if step >= 1 else 0      # (bad arguments: the engine raises before ncols is used)
+        return start, stop, step, ncols
+
+    def posterior_columns(self, c=0, start=0, stop=None, step=1, dtype=np.float64, normalize=True):
+        """Columns `range(start, stop, step)` of the posterior of contig `c` as `[M, ncols]` in `dtype` (float64 or float32):
+        normalised to sum to one per column, or (`normalize=False`) the stored values, bit for bit those of `gammas[c]`.  The
+        matrix is transposed (and normalised) on the device."""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError("posterior_columns: dtype must be float64 or float32")
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        out = np.empty((self.M, ncols), dtype=dtype)
+        E.check(E.lib().smcpp_posterior_columns(self._im, int(c), start, stop, step, int(bool(normalize)),
+                                                int(dtype == np.dtype(np.float32)), out.ctypes.data_as(C.c_void_p), None))
+        return out
+
+    def posterior_summary(self, c=0, weights=None, quantiles=(), start=0, stop=None, step=1):
+        """Per selected column of contig `c`, without fetching the matrix: dict of `colsum` (sum over the states), `argmax` (first
+        maximum), `mean` (`sum_m weights[m] p[m, l]`; absent without weights) and `qstate` `[len(quantiles), ncols]`, the first
+        state at which the cumulative posterior reaches each level (at most 8 levels, each in (0, 1))."""
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        q = aca(np.atleast_1d(np.asarray(quantiles, dtype=np.float64)).reshape(-1))
+        w = None if weights is None else aca(weights, dtype=np.float64).reshape(-1)
+        if w is not None and len(w) != self.M:
+            raise RuntimeError(f"posterior_summary: {len(w)} weights for {self.M} hidden states")
+        ret = {"colsum": np.empty(ncols), "argmax": np.empty(ncols, dtype=np.int32), "qstate": np.empty((len(q), ncols), dtype=np.int32)}
+        if w is not None:
+            ret["mean"] = np.empty(ncols)
+        E.check(E.lib().smcpp_posterior_summary(self._im, int(c), start, stop, step, E.dptr(w), len(q), E.dptr(q) if len(q) else None,
+                                                E.dptr(ret["colsum"]), E.iptr(ret["argmax"]), E.dptr(ret.get("mean")),
+                                                E.iptr(ret["qstate"]) if len(q) else None))
+        return ret
+
+    def posterior_windows(self, c=0, window=10_000):
+        """`[M, ceil(P_L / window)]`: the posterior of contig `c` averaged over windows of `window` base pairs (row `l >= 1` covers
+        the base pairs `[P_{l-1}, P_l)`, `P` the cumulative spans of the rows the manager was given; column 0 takes no part)."""
+        nw = C.c_longlong(0)
+        E.check(E.lib().smcpp_posterior_windows(self._im, int(c), int(window), C.byref(nw), None))
+        out = np.empty((self.M, nw.value))
+        E.check(E.lib().smcpp_posterior_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
+        return out
+
     @property
     def xisums(self):
         ret = []

@@ -106,6 +106,9 @@ cdef extern from "smcpp_engine.h":
     int smcpp_set_params_twopop(smcpp_im *im, int Kd, const double *ad, const double *sd, const double *dad, int K1, const double *a1, const double *s1, const double *da1, int K2, const double *a2, const double *s2, const double *da2, double split, int nder) nogil
     int smcpp_host_joint_csfs(int n1, int n2, int a1, int a2, int n_hs, const double *hs, int K1, const double *pa1, const double *ps1, const double *da1, int K2, const double *pa2, const double *ps2, const double *da2, int nder, double split, int Kmc, double *out, double *dout) nogil
     int smcpp_host_prep_twopop(int n1, int n2, int a1, int a2, int n_hs, const double *hs, double polarization_error, int Kd, const double *ad, const double *sd, int K1, const double *pa1, const double *ps1, int K2, const double *pa2, const double *ps2, double split, double theta, double rho, double alpha, int K, const int *keys, double *pi, double *T, double *E) nogil
+    int smcpp_posterior_columns(smcpp_im *im, int contig, long long start, long long stop, long long step, int normalize, int f32, void *out, double *colsum) nogil
+    int smcpp_posterior_summary(smcpp_im *im, int contig, long long start, long long stop, long long step, const double *weights, int nq, const double *q, double *colsum, int *argmax, double *mean, int *qstate) nogil
+    int smcpp_posterior_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
 # --- end generated ---
 
 aca = np.ascontiguousarray
@@ -355,6 +358,72 @@ cdef class _PyInferenceManager:
                 _check(smcpp_get_gamma(self._im, c, &g[0, 0]))
                 ret.append(g)
             return ret
+
+    # ---- posterior products computed on the device (include/smcpp_engine.h: smcpp_posterior_*; same names and arguments as _smcpp.py) ----
+    def _selection(self, c, start, stop, step):
+        c = int(c)
+        if stop is None:
+            stop = int(self._Ls[c]) + 1 if 0 <= c < self._num_hmms else 1   # (a bad contig index: the engine raises)
+        start, stop, step = int(start), int(stop), int(step)
+        ncols = max(0, -(-(stop - start) // step)) if step >= 1 else 0      # (bad arguments: the engine raises before ncols is used)
+        return start, stop, step, ncols
+
+    def posterior_columns(self, c=0, start=0, stop=None, step=1, dtype=np.float64, normalize=True):
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise TypeError("posterior_columns: dtype must be float64 or float32")
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        cdef int M = len(self._hs) - 1, cc = c, nrm = 1 if normalize else 0, f32 = 1 if dtype == np.dtype(np.float32) else 0, rc
+        cdef long long a = start, b = stop, st = step
+        out = np.empty((M, ncols), dtype=dtype)
+        cdef size_t addr = out.ctypes.data
+        with nogil:
+            rc = smcpp_posterior_columns(self._im, cc, a, b, st, nrm, f32, <void *>addr, NULL)
+        _check(rc)
+        return out
+
+    def posterior_summary(self, c=0, weights=None, quantiles=(), start=0, stop=None, step=1):
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        cdef int M = len(self._hs) - 1, cc = c, rc, nq
+        cdef long long a = start, b = stop, st = step
+        cdef np.ndarray[double, ndim=1] q = aca(np.atleast_1d(np.asarray(quantiles, dtype=np.float64)).reshape(-1))
+        cdef np.ndarray[double, ndim=1] w = np.zeros(1) if weights is None else aca(weights, dtype=np.float64).reshape(-1)
+        if weights is not None and len(w) != M:
+            raise RuntimeError("posterior_summary: %d weights for %d hidden states" % (len(w), M))
+        nq = len(q)
+        cdef np.ndarray[double, ndim=1] colsum = np.empty(max(ncols, 1)), mean = np.empty(max(ncols, 1))
+        cdef np.ndarray[int, ndim=1] argmax = np.empty(max(ncols, 1), dtype=np.int32)
+        cdef np.ndarray[int, ndim=1] qstate = np.empty(max(nq * ncols, 1), dtype=np.int32)
+        cdef double *wp = NULL
+        cdef double *qp = NULL
+        cdef double *mp = NULL
+        cdef int *qsp = NULL
+        cdef double *csp = &colsum[0]
+        cdef int *amp = &argmax[0]
+        if weights is not None:
+            wp = &w[0]
+            mp = &mean[0]
+        if nq:
+            qp = &q[0]
+            qsp = &qstate[0]
+        with nogil:
+            rc = smcpp_posterior_summary(self._im, cc, a, b, st, wp, nq, qp, csp, amp, mp, qsp)
+        _check(rc)
+        ret = {"colsum": colsum[:ncols], "argmax": argmax[:ncols], "qstate": qstate[:nq * ncols].reshape(nq, ncols)}
+        if weights is not None:
+            ret["mean"] = mean[:ncols]
+        return ret
+
+    def posterior_windows(self, c=0, window=10_000):
+        cdef int M = len(self._hs) - 1, cc = c, rc
+        cdef long long W = window, nw = 0
+        _check(smcpp_posterior_windows(self._im, cc, W, &nw, NULL))
+        cdef np.ndarray[double, ndim=2] out = np.empty((M, max(nw, 1)))
+        cdef double *op = &out[0, 0]
+        with nogil:
+            rc = smcpp_posterior_windows(self._im, cc, W, &nw, op)
+        _check(rc)
+        return out[:, :nw] if nw < out.shape[1] else out
 
     property xisums:
         def __get__(self):

@@ -309,37 +309,158 @@ const double *smcpp_im::merged_gamma(int c) {
     return d_gamma_user.p;
 }
 
+// ---- posterior products (posterior_dev.hpp) ----
+static void post_need_gamma(smcpp_im *im, int c) {
+    if (!im->estep_done) throw std::runtime_error("posterior products: no E-step has been run on this manager yet");
+    if (!im->gamma_valid) throw std::runtime_error("posterior products: save_gamma was not set for the last E-step");
+    if (c < 0 || c >= im->n_contigs) throw std::runtime_error("contig index out of range");
+}
+
+static long long post_check_selection(smcpp_im *im, int c, long long start, long long stop, long long step) {
+    const long long L = im->user_Ls[c];
+    if (start < 0) throw std::runtime_error("posterior products: start < 0");
+    if (stop > L + 1) throw std::runtime_error("posterior products: stop > L + 1 (the contig has " + std::to_string(L + 1) + " columns)");
+    if (start >= stop) throw std::runtime_error("posterior products: empty column selection (start >= stop)");
+    if (step < 1) throw std::runtime_error("posterior products: step < 1");
+    return (stop - start + step - 1) / step;
+}
+
+// Where the per-row posteriors of contig c lie: [L + 1][Mp] rows of the caller (row 0 unset) and gamma0 for column 0.
+smcpp_im::PostSource smcpp_im::post_source(int c) {
+    HIPCHK(hipSetDevice(device));
+    PostSource s;
+    s.L = user_Ls[c];
+    s.rows = split_spans ? merged_gamma(c) : (const double *)(d_gamma_rows.p + (size_t)contig_base[c] * Mp);
+    s.g0 = d_gamma0.p + (size_t)c * Mp;
+    return s;
+}
+
+// gamma or p on a column selection, transposed on the device (k_post_columns) and copied out; the arguments have been checked.
+void smcpp_im::post_columns(int c, long long start, long long stop, long long step, bool normalize, bool f32, void *out, double *colsum) {
+    const PostSource src = post_source(c);
+    PostSel sel;
+    sel.start = start; sel.step = step; sel.ncols = (stop - start + step - 1) / step;
+    const size_t cells = (size_t)M * sel.ncols;
+    if (out) d_post_out.alloc(f32 ? (cells + 1) / 2 : cells);
+    if (colsum) d_post_colsum.alloc((size_t)sel.ncols);
+    const int need_sum = (normalize && out) || colsum;
+    const dim3 grid((unsigned)ceil_div(sel.ncols, PC_TL));
+    if (f32)
+        hipLaunchKernelGGL(k_post_columns<float>, grid, dim3(256), 0, stream, M, Mp, sel, src.rows, src.g0, need_sum, (int)normalize,
+                           out ? (float *)d_post_out.p : (float *)nullptr, colsum ? d_post_colsum.p : (double *)nullptr);
+    else
+        hipLaunchKernelGGL(k_post_columns<double>, grid, dim3(256), 0, stream, M, Mp, sel, src.rows, src.g0, need_sum, (int)normalize,
+                           out ? d_post_out.p : (double *)nullptr, colsum ? d_post_colsum.p : (double *)nullptr);
+    HIPCHK(hipGetLastError());
+    if (out) HIPCHK(hipMemcpyAsync(out, d_post_out.p, cells * (f32 ? sizeof(float) : sizeof(double)), hipMemcpyDeviceToHost, stream));
+    if (colsum) HIPCHK(hipMemcpyAsync(colsum, d_post_colsum.p, sizeof(double) * sel.ncols, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+}
+
 int smcpp_get_gamma(smcpp_im *im, int c, double *out) {
     API_BEGIN
     if (c < 0 || c >= im->n_contigs) throw std::runtime_error("contig index out of range");
-    const int M = im->M, Mp = im->Mp;
+    const int M = im->M;
     im->fetch_stats();
     if (!im->gamma_valid) {
         std::memcpy(out, &im->h_gamma0[(size_t)c * M], sizeof(double) * M);   // gamma is M x 1 (hmm.cpp:12-14)
         return 0;
     }
-    HIPCHK(hipSetDevice(im->device));
-    if (im->split_spans) {
-        // the pieces of a long row add up to the row's posterior (engine_manager.hpp: build): added on the device, then as below
-        const int Lu = im->user_Ls[c];
-        const double *src = im->merged_gamma(c);
-        std::vector<double> rows((size_t)(Lu + 1) * Mp);
-        HIPCHK(hipMemcpyAsync(rows.data(), src, rows.size() * sizeof(double), hipMemcpyDeviceToHost, im->stream));
-        HIPCHK(hipStreamSynchronize(im->stream));
-        for (int i = 0; i < M; ++i) {
-            out[(size_t)i * (Lu + 1)] = im->h_gamma0[(size_t)c * M + i];
-            for (int l = 1; l <= Lu; ++l) out[(size_t)i * (Lu + 1) + l] = rows[(size_t)l * Mp + i];
-        }
-        return 0;
+    // every column, as stored: the transpose runs on the device (k_post_columns; rows cut into pieces are added up first)
+    im->post_columns(c, 0, (long long)im->user_Ls[c] + 1, 1, false, false, out, nullptr);
+    API_END
+}
+
+int smcpp_posterior_columns(smcpp_im *im, int c, long long start, long long stop, long long step, int normalize, int f32, void *out,
+                            double *colsum) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    post_check_selection(im, c, start, stop, step);
+    if (!out && !colsum) return 0;
+    im->post_columns(c, start, stop, step, normalize != 0, f32 != 0, out, colsum);
+    API_END
+}
+
+int smcpp_posterior_summary(smcpp_im *im, int c, long long start, long long stop, long long step, const double *weights, int nq,
+                            const double *q, double *colsum, int *argmax, double *mean, int *qstate) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    PostSel sel;
+    sel.start = start; sel.step = step; sel.ncols = post_check_selection(im, c, start, stop, step);
+    if (nq < 0 || nq > 8) throw std::runtime_error("posterior summary: between 0 and 8 quantile levels");
+    if (nq > 0 && !q) throw std::runtime_error("posterior summary: quantile levels are missing");
+    PostLevels lv;
+    lv.nq = nq;
+    for (int k = 0; k < 8; ++k) lv.q[k] = 2.0;
+    for (int k = 0; k < nq; ++k) {
+        if (!(q[k] > 0.0 && q[k] < 1.0)) throw std::runtime_error("posterior summary: a quantile level must lie in (0, 1)");
+        lv.q[k] = q[k];
     }
-    const int L = im->Ls[c];
-    std::vector<double> rows((size_t)(L + 1) * Mp);
-    HIPCHK(hipMemcpy(rows.data(), im->d_gamma_rows.p + (size_t)im->contig_base[c] * Mp, rows.size() * sizeof(double),
-                     hipMemcpyDeviceToHost));
-    for (int i = 0; i < M; ++i) {
-        out[(size_t)i * (L + 1)] = im->h_gamma0[(size_t)c * M + i];
-        for (int l = 1; l <= L; ++l) out[(size_t)i * (L + 1) + l] = rows[(size_t)l * Mp + i];
+    const int M = im->M;
+    if (weights)
+        for (int i = 0; i < M; ++i)
+            if (!std::isfinite(weights[i])) throw std::runtime_error("posterior summary: weight " + std::to_string(i) + " is not finite");
+    const bool want_mean = weights && mean, want_q = nq > 0 && qstate;
+    if (!colsum && !argmax && !want_mean && !want_q) return 0;
+    const smcpp_im::PostSource src = im->post_source(c);
+    hipStream_t s = im->stream;
+    if (colsum) im->d_post_colsum.alloc((size_t)sel.ncols);
+    if (argmax) im->d_post_arg.alloc((size_t)sel.ncols);
+    if (want_mean) {
+        im->d_post_mean.alloc((size_t)sel.ncols);
+        im->d_post_w.alloc((size_t)M);
+        HIPCHK(hipMemcpyAsync(im->d_post_w.p, weights, sizeof(double) * M, hipMemcpyHostToDevice, s));
     }
+    if (want_q) im->d_post_q.alloc((size_t)nq * sel.ncols);
+    else lv.nq = 0;
+    hipLaunchKernelGGL(k_post_summary, dim3((unsigned)ceil_div(sel.ncols, PS_TL)), dim3(256), 0, s, M, im->Mp, sel, src.rows, src.g0,
+                       want_mean ? (const double *)im->d_post_w.p : (const double *)nullptr, lv,
+                       colsum ? im->d_post_colsum.p : (double *)nullptr, argmax ? im->d_post_arg.p : (int *)nullptr,
+                       want_mean ? im->d_post_mean.p : (double *)nullptr, want_q ? im->d_post_q.p : (int *)nullptr);
+    HIPCHK(hipGetLastError());
+    if (colsum) HIPCHK(hipMemcpyAsync(colsum, im->d_post_colsum.p, sizeof(double) * sel.ncols, hipMemcpyDeviceToHost, s));
+    if (argmax) HIPCHK(hipMemcpyAsync(argmax, im->d_post_arg.p, sizeof(int) * sel.ncols, hipMemcpyDeviceToHost, s));
+    if (want_mean) HIPCHK(hipMemcpyAsync(mean, im->d_post_mean.p, sizeof(double) * sel.ncols, hipMemcpyDeviceToHost, s));
+    if (want_q) HIPCHK(hipMemcpyAsync(qstate, im->d_post_q.p, sizeof(int) * (size_t)nq * sel.ncols, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
+int smcpp_posterior_windows(smcpp_im *im, int c, long long window_bp, long long *n_windows, double *out) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    if (window_bp < 1) throw std::runtime_error("posterior windows: window_bp < 1");
+    const std::vector<long long> &P = im->user_prefix[c];
+    const long long L = im->user_Ls[c];
+    const long long nwin = (P[L] + window_bp - 1) / window_bp;
+    if (n_windows) *n_windows = nwin;
+    if (!out) return 0;
+    if (nwin > (1LL << 31) - 1 - PW_WPB) throw std::runtime_error("posterior windows: too many windows for one launch (widen the window)");
+    const smcpp_im::PostSource src = im->post_source(c);
+    hipStream_t s = im->stream;
+    const int M = im->M, Mp = im->Mp;
+    if (im->d_user_prefix.size() != (size_t)im->n_contigs) im->d_user_prefix.resize(im->n_contigs);
+    if (!im->d_user_prefix[c].p) {
+        im->d_user_prefix[c].upload(P, s);             // (P is a member: it outlives the copy)
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    // the column sums of every row, by the kernel that serves smcpp_posterior_summary: p is the same number in every product
+    PostSel all;
+    all.start = 0; all.step = 1; all.ncols = L + 1;
+    PostLevels none;
+    none.nq = 0;
+    for (int k = 0; k < 8; ++k) none.q[k] = 2.0;
+    im->d_post_colsum.alloc((size_t)L + 1);
+    hipLaunchKernelGGL(k_post_summary, dim3((unsigned)ceil_div(all.ncols, PS_TL)), dim3(256), 0, s, M, Mp, all, src.rows, src.g0,
+                       (const double *)nullptr, none, im->d_post_colsum.p, (int *)nullptr, (double *)nullptr, (int *)nullptr);
+    HIPCHK(hipGetLastError());
+    im->d_post_out.alloc((size_t)M * nwin);
+    hipLaunchKernelGGL(k_post_windows, dim3((unsigned)ceil_div(nwin, PW_WPB), (unsigned)ceil_div(M, 64)), dim3(256), 0, s, M, Mp, L,
+                       window_bp, nwin, (const long long *)im->d_user_prefix[c].p, src.rows, (const double *)im->d_post_colsum.p,
+                       im->d_post_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, im->d_post_out.p, sizeof(double) * (size_t)M * nwin, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     API_END
 }
 

@@ -192,6 +192,15 @@ struct smcpp_im {
     std::vector<DevBuf<int>> d_piece_first;       // per contig: first piece of every caller's row ([Lu + 2]; k_gamma_merge)
     DevBuf<double> d_gamma_user;                  // the caller's rows of ONE contig, pieces added up: [Lu + 1][Mp]
     const double *merged_gamma(int c);            // (device pointer; row 0 unset)
+    // posterior products (posterior_dev.hpp, smcpp_posterior_*): prefix positions of the CALLER's rows per contig ([Lu + 1], entry 0 =
+    // 0; built in build(), uploaded on first use) and the device side of the outputs
+    std::vector<std::vector<long long>> user_prefix;
+    std::vector<DevBuf<long long>> d_user_prefix;
+    DevBuf<double> d_post_out, d_post_colsum, d_post_mean, d_post_w;
+    DevBuf<int> d_post_arg, d_post_q;
+    struct PostSource { const double *rows, *g0; int L; };
+    PostSource post_source(int c);                // (after the argument checks: may launch k_gamma_merge)
+    void post_columns(int c, long long start, long long stop, long long step, bool normalize, bool f32, void *out, double *colsum);
     // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;
@@ -390,12 +399,17 @@ void smcpp_im::build(int npop_, const int *nn, const int *nna, int n_contigs_, c
         const int ncol_ = 1 + keylen;
         long long rows = 0, pieces = 0;
         int maxspan = 0;
-        for (int c = 0; c < n_contigs; ++c)
+        user_prefix.assign(n_contigs, std::vector<long long>());
+        for (int c = 0; c < n_contigs; ++c) {
+            std::vector<long long> &pp = user_prefix[c];
+            pp.assign((size_t)std::max(Ls[c], 0) + 1, 0);
             for (int i = 0; i < Ls[c]; ++i) {
                 const int sp = obs[c][(size_t)i * ncol_];
                 if (sp <= 0) throw std::runtime_error("data are malformed: span <= 0");
                 rows++; pieces += (sp + 63) / 64; maxspan = std::max(maxspan, sp);
+                pp[(size_t)i + 1] = pp[i] + sp;
             }
+        }
         const bool want = M > 64 && !opt().off(smcpp_opt::O_SPLIT_SPANS);      // (M <= 64: the one-state-per-lane chains have no un-floored store)
         // (beyond 256 states there is no other path: un-binned rows are cut as well - the chains then walk every position, which is
         // what a row costs there anyway - as long as the pieces' alpha / beta rows fit a third of a 288 GB device)

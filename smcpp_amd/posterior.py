@@ -27,20 +27,10 @@ def balance_hidden_states(model, M):
     return np.array(ret)
 
 
-def posterior(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
-              start=None, end=None, thinning=1, return_manager=False):
-    """Posterior decoding of each contig.  Returns `(hidden_states, gammas, sites, paths)`:
-    `gammas[c]` is `[M, L+1]` with columns normalised to one (`posterior.py:102-106`), `sites[c]` the span column of the
-    rows handed to the manager (missing row included) exactly as the reference stores it under `<file>_sites`
-    (`posterior.py:109`: `obs[:, 0]`, one entry per row; cumulative positions are `np.cumsum` of it), `paths[c]` the
-    argmax state per column computed on the device.  `return_manager=True` appends the inference manager (its device buffers
-    stay allocated for as long as the caller keeps it) - nothing is kept otherwise.
-    A missing row is prepended to every contig as the reference does (`posterior.py:83`); `start` / `end` keep the rows whose
-    cumulative position lies in [start, end] (`posterior.py:76-82`: "only approximately picked out"), `thinning` > 1 thins every
-    contig as `thin_dataset` does (`posterior.py:85-87`).
-    TWO populations (`posterior.py:88-100`): `n = (n1, n2)` undistinguished and `a = (a1, a2)` distinguished lineages per
-    population, rows of 7 columns, `model` a `TwoPopulationModel`; the hidden states are balanced with respect to the
-    DISTINGUISHED lineages' model (`m.distinguished_model`, `posterior.py:60-62`)."""
+def _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end, thinning):
+    """What `posterior` and `posterior_products` share: the hidden states, the rows handed to the manager (missing row in front,
+    `start` / `end` / `thinning` applied) and a one- or two-population manager after its `save_gamma` E-step.
+    -> `(hidden_states, obs, im)`."""
     twopop = not np.isscalar(n) and len(n) == 2
     dist = model.model1 if twopop else model          # `distinguished_model` (smcpp/model.py:70-72,275-277)
     hs = balance_hidden_states(dist, M) if hidden_states is None else np.asarray(hidden_states, dtype=float)
@@ -73,6 +63,25 @@ def posterior(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.
     im.alpha = alpha
     im.save_gamma = True
     im.E_step()
+    return hs, obs, im
+
+
+def posterior(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
+              start=None, end=None, thinning=1, return_manager=False):
+    """Posterior decoding of each contig.  Returns `(hidden_states, gammas, sites, paths)`:
+    `gammas[c]` is `[M, L+1]` with columns normalised to one (`posterior.py:102-106`), `sites[c]` the span column of the
+    rows handed to the manager (missing row included) exactly as the reference stores it under `<file>_sites`
+    (`posterior.py:109`: `obs[:, 0]`, one entry per row; cumulative positions are `np.cumsum` of it), `paths[c]` the
+    argmax state per column computed on the device.  `return_manager=True` appends the inference manager (its device buffers
+    stay allocated for as long as the caller keeps it) - nothing is kept otherwise.
+    A missing row is prepended to every contig as the reference does (`posterior.py:83`); `start` / `end` keep the rows whose
+    cumulative position lies in [start, end] (`posterior.py:76-82`: "only approximately picked out"), `thinning` > 1 thins every
+    contig as `thin_dataset` does (`posterior.py:85-87`).
+    TWO populations (`posterior.py:88-100`): `n = (n1, n2)` undistinguished and `a = (a1, a2)` distinguished lineages per
+    population, rows of 7 columns, `model` a `TwoPopulationModel`; the hidden states are balanced with respect to the
+    DISTINGUISHED lineages' model (`m.distinguished_model`, `posterior.py:60-62`)."""
+    hs, obs, im = _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end,
+                                thinning)
     gammas, sites, paths = [], [], []
     for c, g in enumerate(im.gammas):
         g = g / g.sum(axis=0, keepdims=True)
@@ -84,10 +93,61 @@ def posterior(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.
     return hs, gammas, sites, paths
 
 
+def average_coal_times(model, hidden_states):
+    """E[T | hs_m <= T < hs_{m+1}] under `model` for every hidden state, coalescent units (`PyRateFunction.average_coal_times`,
+    `_smcpp.pyx:370-389`).  Finite in the last, unbounded state as well."""
+    a = np.asarray(model.stepwise_values(), dtype=float)
+    s = np.asarray(model.s, dtype=float)
+    _, ct = _engine.host_rate_function(a, s, [0.0], hs=np.asarray(hidden_states, dtype=float))
+    return ct
+
+
+def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
+                       start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False):
+    """What a posterior decoding is reduced to, computed on the device without ever fetching the `[M, L+1]` matrix (arguments and
+    set-up as `posterior`: hidden states, the prepended missing row, `start` / `end` / `thinning`, one or two populations).
+    Returns `(hidden_states, products)`; `products[c]` is a dict for contig c:
+      `sites`       the span column of the rows handed to the manager, as `posterior` returns it;
+      `path`        argmax state per column, `[L+1]` int32 (`posterior`'s `paths[c]`);
+      `mean_tmrca`  posterior mean of the coalescence time per column, `[L+1]`, coalescent units: `sum_m w_m p[m, l]` with `w_m`
+                    the average coalescence time of hidden state m under the distinguished model (`average_coal_times`);
+      `qstate`      `[len(quantiles), L+1]` int32: the first state at which the cumulative posterior reaches each level (a credible
+                    band in units of hidden states; at most 8 levels);
+      `windows`     only with `window=W` base pairs: `[M, ceil(P / W)]`, the posterior averaged over windows of W base pairs, P the
+                    total span of the rows handed to the manager.  Position 0 of the window axis is the PREPENDED MISSING ROW (span
+                    1), not the first base pair of the caller's contig: window w covers the caller's base pairs [w W - 1, (w + 1) W - 1).
+    `return_manager=True` appends the inference manager."""
+    hs, obs, im = _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end,
+                                thinning)
+    twopop = not np.isscalar(n) and len(n) == 2
+    w = average_coal_times(model.model1 if twopop else model, hs)
+    products = []
+    for c in range(len(obs)):
+        sm = im.posterior_summary(c, weights=w, quantiles=quantiles)
+        prod = {"sites": obs[c][:, 0].copy(), "path": sm["argmax"], "mean_tmrca": sm["mean"], "qstate": sm["qstate"]}
+        if window is not None:
+            prod["windows"] = im.posterior_windows(c, window)
+        products.append(prod)
+    if return_manager:
+        return hs, products, im
+    return hs, products
+
+
 def save_npz(path, hs, gammas, sites, names):
     """`.npz` layout of `smc++ posterior` (README.rst:348-372): `hidden_states`, `<file>`, `<file>_sites`."""
     out = {"hidden_states": hs}
     for nm, g, s in zip(names, gammas, sites):
         out[nm] = g
         out[nm + "_sites"] = s
+    np.savez_compressed(path, **out)
+
+
+def save_products_npz(path, hs, products, names):
+    """`.npz` of `posterior_products`: `hidden_states` and per file `<file>_sites`, `<file>_path`, `<file>_mean_tmrca`,
+    `<file>_qstate` and, where windows were asked for, `<file>_windows`."""
+    out = {"hidden_states": hs}
+    for nm, prod in zip(names, products):
+        for key in ("sites", "path", "mean_tmrca", "qstate", "windows"):
+            if key in prod:
+                out[f"{nm}_{key}"] = prod[key]
     np.savez_compressed(path, **out)
