@@ -347,6 +347,34 @@ int smcpp_posterior_summary(smcpp_im *im, int contig, long long start, long long
 int smcpp_posterior_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
                             double *out /* [M x n_windows]; NULL: only n_windows is written */);
 
+/* ---- posterior transition products on the device (no reference counterpart; smcpp_amd/csrc/posterior_trans_dev.hpp) --- */
+
+/* Where the hidden state changes along a contig, from the vectors the LAST E-step stored (it must have run with save_gamma, and
+ * the parameters must not have been set again since).  Row l of contig `contig` has span s_l and key k_l and covers positions
+ * P_{l-1} + 1 .. P_l.  For a position p of row l, with x_{p-1} the forward vector before it, y_p the backward vector after it and
+ * e = E[k_l] the row's emission vector,
+ *     xi_p(i, j) = x_{p-1}(i) T(i, j) e(j) y_p(j) / Z_p,        Z_p = sum_ij of the numerator,
+ *     stay[l] = sum_{p in row l} sum_i xi_p(i, i),
+ *     up[l]   = sum_{p in row l} sum_{i<j} xi_p(i, j)           (to a higher index = older state),
+ *     down[l] = sum_{p in row l} sum_{i>j} xi_p(i, j),
+ * so stay + up + down = s_l, s_l - stay[l] is the expected number of state changes in the row, and the sums over the rows of a
+ * contig are the trace and the strict upper / lower triangle sums of its xisum.  Column 0, which no transition enters, holds
+ * (0, 0, 0).  x and y are scale free: they start from the stored float alpha at the row's start and the stored beta at its end and
+ * are advanced through the row's interior by the O(M) scan steps of the semiseparable transition matrix; where the plan cut long
+ * rows, the pieces of a caller's row are added up on the device.  Results do not depend on the launch shape or on call order.
+ * Each call fails before anything is launched when no E-step has run, the last one ran without save_gamma, the contig index is out
+ * of range, start < 0, stop > L + 1, start >= stop, step < 1, window_bp < 1, the parameters were set again after the last E-step,
+ * or the transition matrix lacks the semiseparable structure (smcpp_set_raw with an arbitrary matrix).
+ *
+ * smcpp_posterior_transitions: the three values on the column selection range(start, stop, step) over 0 .. L. */
+int smcpp_posterior_transitions(smcpp_im *im, int contig, long long start, long long stop, long long step,
+                                double *stay, double *up, double *down /* each [ncols] or NULL */);
+/* smcpp_posterior_transition_windows: expected counts per window of window_bp base pairs, a row apportioned uniformly over its
+ * base pairs: out[x, w] = sum_l overlap(l, w) / s_l * x[l] for x = stay, up, down, rows added in ascending order (windows as in
+ * smcpp_posterior_windows).  The three values of a window sum to its covered base pairs.  *n_windows = ceil(P_L / W). */
+int smcpp_posterior_transition_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
+                                       double *out /* [3 x n_windows] row-major; NULL: only n_windows */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,25 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_posterior_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
         return out
 
+    def posterior_transitions(self, c=0, start=0, stop=None, step=1):
+        """Where the hidden state changes: dict of `stay`, `up`, `down`, each `[ncols]` over the columns `range(start, stop, step)` of
+        contig `c` - the expected number of the row's positions at which the state stays, moves to a higher index (an older state)
+        or to a lower one.  They sum to the row's span; column 0 holds zeros.  (include/smcpp_engine.h: smcpp_posterior_transitions.)"""
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        ret = {k: np.empty(ncols) for k in ("stay", "up", "down")}
+        E.check(E.lib().smcpp_posterior_transitions(self._im, int(c), start, stop, step, E.dptr(ret["stay"]), E.dptr(ret["up"]),
+                                                    E.dptr(ret["down"])))
+        return ret
+
+    def posterior_transition_windows(self, c=0, window=10_000):
+        """`[3, ceil(P_L / window)]`: expected stay / up / down counts of contig `c` per window of `window` base pairs, every row
+        apportioned uniformly over its base pairs; the three rows of a window sum to its covered base pairs."""
+        nw = C.c_longlong(0)
+        E.check(E.lib().smcpp_posterior_transition_windows(self._im, int(c), int(window), C.byref(nw), None))
+        out = np.empty((3, nw.value))
+        E.check(E.lib().smcpp_posterior_transition_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
+        return out
+
     @property
     def xisums(self):
         ret = []

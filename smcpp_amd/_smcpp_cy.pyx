@@ -109,6 +109,8 @@ cdef extern from "smcpp_engine.h":
     int smcpp_posterior_columns(smcpp_im *im, int contig, long long start, long long stop, long long step, int normalize, int f32, void *out, double *colsum) nogil
     int smcpp_posterior_summary(smcpp_im *im, int contig, long long start, long long stop, long long step, const double *weights, int nq, const double *q, double *colsum, int *argmax, double *mean, int *qstate) nogil
     int smcpp_posterior_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
+    int smcpp_posterior_transitions(smcpp_im *im, int contig, long long start, long long stop, long long step, double *stay, double *up, double *down) nogil
+    int smcpp_posterior_transition_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
 # --- end generated ---
 
 aca = np.ascontiguousarray
@@ -422,6 +424,30 @@ cdef class _PyInferenceManager:
         cdef double *op = &out[0, 0]
         with nogil:
             rc = smcpp_posterior_windows(self._im, cc, W, &nw, op)
+        _check(rc)
+        return out[:, :nw] if nw < out.shape[1] else out
+
+    def posterior_transitions(self, c=0, start=0, stop=None, step=1):
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        cdef int cc = c, rc
+        cdef long long a = start, b = stop, st = step
+        cdef np.ndarray[double, ndim=2] out = np.empty((3, max(ncols, 1)))
+        cdef double *p0 = &out[0, 0]
+        cdef double *p1 = &out[1, 0]
+        cdef double *p2 = &out[2, 0]
+        with nogil:
+            rc = smcpp_posterior_transitions(self._im, cc, a, b, st, p0, p1, p2)
+        _check(rc)
+        return {"stay": out[0, :ncols].copy(), "up": out[1, :ncols].copy(), "down": out[2, :ncols].copy()}
+
+    def posterior_transition_windows(self, c=0, window=10_000):
+        cdef int cc = c, rc
+        cdef long long W = window, nw = 0
+        _check(smcpp_posterior_transition_windows(self._im, cc, W, &nw, NULL))
+        cdef np.ndarray[double, ndim=2] out = np.empty((3, max(nw, 1)))
+        cdef double *op = &out[0, 0]
+        with nogil:
+            rc = smcpp_posterior_transition_windows(self._im, cc, W, &nw, op)
         _check(rc)
         return out[:, :nw] if nw < out.shape[1] else out
 

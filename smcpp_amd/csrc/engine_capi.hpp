@@ -294,6 +294,17 @@ int smcpp_get_xisum(smcpp_im *im, int c, double *out) {
 // The caller's rows of contig c with the pieces of every cut row added up, on the device ([Lu + 1][Mp]; row 0 is left to the caller).
 const double *smcpp_im::merged_gamma(int c) {
     const int Lu = user_Ls[c];
+    const int *first = piece_first_dev(c);
+    d_gamma_user.alloc((size_t)(Lu + 1) * Mp);
+    hipLaunchKernelGGL(k_gamma_merge, dim3((unsigned)ceil_div((long long)Lu * Mp, 256)), dim3(256), 0, stream, Mp, Lu,
+                       first, (const double *)(d_gamma_rows.p + (size_t)contig_base[c] * Mp), d_gamma_user.p);
+    return d_gamma_user.p;
+}
+
+// first[l] = the first piece (engine row) of caller's row l of contig c, first[Lu + 1] = one past the last piece; built on first use.
+const int *smcpp_im::piece_first_dev(int c) {
+    if (!split_spans) return nullptr;
+    const int Lu = user_Ls[c];
     if (d_piece_first.size() != (size_t)n_contigs) d_piece_first.resize(n_contigs);
     if (!d_piece_first[c].p) {
         std::vector<int> first((size_t)Lu + 2, 0);
@@ -303,10 +314,7 @@ const double *smcpp_im::merged_gamma(int c) {
         d_piece_first[c].upload(first, stream);
         HIPCHK(hipStreamSynchronize(stream));          // (`first` is a local: the copy has to be done before it goes)
     }
-    d_gamma_user.alloc((size_t)(Lu + 1) * Mp);
-    hipLaunchKernelGGL(k_gamma_merge, dim3((unsigned)ceil_div((long long)Lu * Mp, 256)), dim3(256), 0, stream, Mp, Lu,
-                       (const int *)d_piece_first[c].p, (const double *)(d_gamma_rows.p + (size_t)contig_base[c] * Mp), d_gamma_user.p);
-    return d_gamma_user.p;
+    return d_piece_first[c].p;
 }
 
 // ---- posterior products (posterior_dev.hpp) ----
@@ -460,6 +468,111 @@ int smcpp_posterior_windows(smcpp_im *im, int c, long long window_bp, long long 
                        im->d_post_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, im->d_post_out.p, sizeof(double) * (size_t)M * nwin, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
+// ---- posterior transition products (posterior_trans_dev.hpp) ----
+void smcpp_im::post_transitions_check() {
+    if (dirty)
+        throw std::runtime_error("posterior transitions: the parameters were set again after the last E-step, whose stored vectors "
+                                 "belong to the earlier ones: run the E-step again");
+    // the scan chains of the last E-step ran on these generators; an E-step on the dense kernels (long un-cut rows beyond 64
+    // states, SMCPP_SS=0, SMCPP_CHAIN, SMCPP_HYBRID=0) stored the same vectors: its T is looked at here
+    if (!ss_active && !ss_generators_only())
+        throw std::runtime_error("posterior transitions: the transition matrix does not have the semiseparable structure of the "
+                                 "model's (smcpp_set_raw with an arbitrary matrix): the O(M) steps that walk a row's interior do "
+                                 "not exist for it");
+    if ((int)ss_gen.size() != 10 * 64 * NPL) throw std::runtime_error("posterior transitions: the generators of T are missing");
+}
+
+// stay / up / down of caller's rows start, start + step, .. (ncols of them) of contig c: [3][ncols] on the device, on `stream`.
+// The arguments have been checked.
+const double *smcpp_im::post_transitions(int c, long long start, long long step, long long ncols) {
+    HIPCHK(hipSetDevice(device));
+    const int MS = 64 * NPL, Le = Ls[c];
+    const int *first = piece_first_dev(c);
+    d_pt_gen.upload(ss_gen, stream);                   // (ss_gen is a member: it outlives the copy)
+    SsArgs sa = SsArgs();
+    sa.M = M; sa.Mp = Mp;
+    const double *gd = d_pt_gen.p;
+    sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
+    sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
+    sa.c0 = ss_c0;
+    PtArgs pa;
+    pa.M = M; pa.Mp = Mp; pa.L = Le; pa.base = contig_base[c];
+    int smax = 1;                                      // the contig's longest engine row
+    for (int i = 1; i <= Le; ++i) {
+        const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+        if (ri.gid >= 0) smax = std::max(smax, groups[ri.gid].span);
+    }
+    pa.nck = (smax + PT_BLK - 1) / PT_BLK - 1;
+    // one wavefront per row, persistent; fewer of them where the scratch of a wavefront is large (many states per lane, or the
+    // checkpoints of a very long row): at most 1 GiB in all
+    const size_t per_wave = (size_t)PT_BLK * 3 * MS * sizeof(float) + (size_t)pa.nck * MS * sizeof(double);
+    const long long want = std::min<long long>(Le, NPL >= 8 ? 1024 : 4096);
+    const int nw = (int)std::max<long long>(1, std::min<long long>(want, (long long)((1ull << 30) / per_wave)));
+    d_pt_park.alloc((size_t)nw * PT_BLK * 3 * MS);
+    d_pt_ckpt.alloc(std::max<size_t>(1, (size_t)nw * pa.nck * MS));
+    d_pt_eng.alloc((size_t)3 * (Le + 1));
+    pa.rowinfo = d_rowinfo.p; pa.g_span = d_g_span.p; pa.E = d_E.p; pa.alpha = d_alpha.p; pa.beta = d_beta.p;
+    pa.park = d_pt_park.p; pa.ckpt = d_pt_ckpt.p; pa.out = d_pt_eng.p;
+    const dim3 grid(ceil_div(nw, 4)), block(256);
+    switch (NPL) {
+#define PT_(x) case x: hipLaunchKernelGGL((k_post_transitions<x>), grid, block, 0, stream, sa, pa, nw); break;
+        PT_(1) PT_(2) PT_(3) PT_(4) PT_(8)
+        default: PT_(16)
+#undef PT_
+    }
+    HIPCHK(hipGetLastError());
+    PostSel sel;
+    sel.start = start; sel.step = step; sel.ncols = ncols;
+    d_pt_sel.alloc((size_t)3 * ncols);
+    hipLaunchKernelGGL(k_post_transitions_select, dim3((unsigned)ceil_div(ncols, 256)), dim3(256), 0, stream, sel, (long long)Le, first,
+                       (const double *)d_pt_eng.p, d_pt_sel.p);
+    HIPCHK(hipGetLastError());
+    return d_pt_sel.p;
+}
+
+int smcpp_posterior_transitions(smcpp_im *im, int c, long long start, long long stop, long long step, double *stay, double *up,
+                                double *down) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    const long long ncols = post_check_selection(im, c, start, stop, step);
+    im->post_transitions_check();
+    if (!stay && !up && !down) return 0;
+    const double *d = im->post_transitions(c, start, step, ncols);
+    hipStream_t s = im->stream;
+    double *dst[3] = {stay, up, down};
+    for (int x = 0; x < 3; ++x)
+        if (dst[x]) HIPCHK(hipMemcpyAsync(dst[x], d + (size_t)x * ncols, sizeof(double) * ncols, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
+int smcpp_posterior_transition_windows(smcpp_im *im, int c, long long window_bp, long long *n_windows, double *out) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    if (window_bp < 1) throw std::runtime_error("posterior transition windows: window_bp < 1");
+    im->post_transitions_check();
+    const std::vector<long long> &P = im->user_prefix[c];
+    const long long L = im->user_Ls[c];
+    const long long nwin = (P[L] + window_bp - 1) / window_bp;
+    if (n_windows) *n_windows = nwin;
+    if (!out) return 0;
+    if (nwin > 4 * ((1LL << 31) - 1)) throw std::runtime_error("posterior transition windows: too many windows for one launch (widen the window)");
+    const double *v = im->post_transitions(c, 0, 1, L + 1);
+    hipStream_t s = im->stream;
+    if (im->d_user_prefix.size() != (size_t)im->n_contigs) im->d_user_prefix.resize(im->n_contigs);
+    if (!im->d_user_prefix[c].p) {
+        im->d_user_prefix[c].upload(P, s);             // (P is a member: it outlives the copy)
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    im->d_post_out.alloc((size_t)3 * nwin);
+    hipLaunchKernelGGL(k_post_transition_windows, dim3((unsigned)ceil_div(nwin, 4)), dim3(256), 0, s, L, window_bp, nwin,
+                       (const long long *)im->d_user_prefix[c].p, v, im->d_post_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, im->d_post_out.p, sizeof(double) * (size_t)3 * nwin, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     API_END
 }

@@ -131,6 +131,11 @@ struct smcpp_im {
     // M = 256 - and the entry-by-entry structure check of the expanded matrix - 58 us - leave the critical path in front of the chains;
     // host_prep_and_upload expands it for the statistics while the chains run
     bool T_lazy = false;
+    // ... and the scan chains keep taking their operator from the generators for as long as these parameters stand, also after the
+    // matrix was expanded (by the statistics of the first E-step, or by a getter): an E-step repeated with the same parameters runs
+    // on the same generators, bit for bit, whoever read T in between (the generators extracted back from the expanded matrix differ
+    // from them in the last bits)
+    bool T_from_gen = false;
     smcpp_host::TransitionGenerators<double> tgen_g;
     void ensure_T() { if (T_lazy) { T = smcpp_host::transition_expand<double>(tgen_g); T_lazy = false; } }
     struct QDev {
@@ -201,6 +206,13 @@ struct smcpp_im {
     struct PostSource { const double *rows, *g0; int L; };
     PostSource post_source(int c);                // (after the argument checks: may launch k_gamma_merge)
     void post_columns(int c, long long start, long long stop, long long step, bool normalize, bool f32, void *out, double *colsum);
+    // posterior transition products (posterior_trans_dev.hpp, smcpp_posterior_transition*): the generators of the last E-step's T, the
+    // wavefronts' scratch (parked addends, checkpoints of long rows), the products per engine row and per selected caller's row
+    DevBuf<double> d_pt_gen, d_pt_ckpt, d_pt_eng, d_pt_sel;
+    DevBuf<float> d_pt_park;
+    const int *piece_first_dev(int c);            // first piece of every caller's row of contig c on the device; nullptr: no row is cut
+    void post_transitions_check();                // throws unless the stored vectors and a structured T are there
+    const double *post_transitions(int c, long long start, long long step, long long ncols);   // -> [3][ncols] on the device
     // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;

@@ -162,7 +162,7 @@ void smcpp_im::dev_prepare() {
         }
         dprep->set_keys(*prep1, pk, Kp_, local, slot, maxspan, K, M, Mp, ss_static ? 64 * NPL : 0);
     }
-    T_lazy = false;
+    T_lazy = T_from_gen = false;
     if (nder > 0) {
         HostTrace tr;
         smcpp_host::DualScope sc(nder);
@@ -200,7 +200,7 @@ void smcpp_im::dev_prepare() {
         tgen_valid = tgen.ok;
         // (the expansion waits until somebody reads the matrix - ensure_T; without usable generators, or with SMCPP_T_LAZY=0: here)
         tgen_g = std::move(g);
-        T_lazy = tgen_valid && !opt().off(smcpp_opt::O_T_LAZY);
+        T_lazy = T_from_gen = tgen_valid && !opt().off(smcpp_opt::O_T_LAZY);
         if (!T_lazy) T = smcpp_host::transition_expand<double>(tgen_g);
         tr.mark("prep: T expand");
         dpi.clear(); dT.clear();

@@ -484,7 +484,7 @@ static bool ss_generators_from_tgen(int M, int MS, const smcpp_host::TransitionG
 }
 
 bool smcpp_im::ss_generators_only() {
-    if (T_lazy && tgen_valid && ss_generators_from_tgen(M, 64 * NPL, tgen, ss_gen, ss_c0)) {
+    if ((T_lazy || T_from_gen) && tgen_valid && ss_generators_from_tgen(M, 64 * NPL, tgen, ss_gen, ss_c0)) {
         // (no expanded matrix yet, and none needed by the chains)
     } else {
         ensure_T();

@@ -103,7 +103,7 @@ def average_coal_times(model, hidden_states):
 
 
 def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
-                       start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False):
+                       start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False, transitions=False):
     """What a posterior decoding is reduced to, computed on the device without ever fetching the `[M, L+1]` matrix (arguments and
     set-up as `posterior`: hidden states, the prepended missing row, `start` / `end` / `thinning`, one or two populations).
     Returns `(hidden_states, products)`; `products[c]` is a dict for contig c:
@@ -116,6 +116,12 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
       `windows`     only with `window=W` base pairs: `[M, ceil(P / W)]`, the posterior averaged over windows of W base pairs, P the
                     total span of the rows handed to the manager.  Position 0 of the window axis is the PREPENDED MISSING ROW (span
                     1), not the first base pair of the caller's contig: window w covers the caller's base pairs [w W - 1, (w + 1) W - 1).
+    With `transitions=True` (one-population or two-population models alike) each dict gains
+      `transitions`         `[3, L+1]`: per column the expected number of the row's positions at which the hidden state stays, moves
+                            up (to an older state) or moves down; the three sum to the row's span, column 0 holds zeros
+                            (`im.posterior_transitions`);
+      `transition_windows`  only with `window=W`: `[3, ceil(P / W)]`, the same counts per window of W base pairs, a row
+                            apportioned uniformly over its base pairs (windows as for `windows`).
     `return_manager=True` appends the inference manager."""
     hs, obs, im = _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end,
                                 thinning)
@@ -127,6 +133,11 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
         prod = {"sites": obs[c][:, 0].copy(), "path": sm["argmax"], "mean_tmrca": sm["mean"], "qstate": sm["qstate"]}
         if window is not None:
             prod["windows"] = im.posterior_windows(c, window)
+        if transitions:
+            tr = im.posterior_transitions(c)
+            prod["transitions"] = np.stack([tr["stay"], tr["up"], tr["down"]])
+            if window is not None:
+                prod["transition_windows"] = im.posterior_transition_windows(c, window)
         products.append(prod)
     if return_manager:
         return hs, products, im
@@ -144,10 +155,10 @@ def save_npz(path, hs, gammas, sites, names):
 
 def save_products_npz(path, hs, products, names):
     """`.npz` of `posterior_products`: `hidden_states` and per file `<file>_sites`, `<file>_path`, `<file>_mean_tmrca`,
-    `<file>_qstate` and, where windows were asked for, `<file>_windows`."""
+    `<file>_qstate` and, where they were asked for, `<file>_windows`, `<file>_transitions`, `<file>_transition_windows`."""
     out = {"hidden_states": hs}
     for nm, prod in zip(names, products):
-        for key in ("sites", "path", "mean_tmrca", "qstate", "windows"):
+        for key in ("sites", "path", "mean_tmrca", "qstate", "windows", "transitions", "transition_windows"):
             if key in prod:
                 out[f"{nm}_{key}"] = prod[key]
     np.savez_compressed(path, **out)
