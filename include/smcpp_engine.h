@@ -375,6 +375,39 @@ int smcpp_posterior_transitions(smcpp_im *im, int contig, long long start, long 
 int smcpp_posterior_transition_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
                                        double *out /* [3 x n_windows] row-major; NULL: only n_windows */);
 
+/* ---- posterior paths (posterior_paths_dev.hpp): joint draws of the hidden-state path of contig c from the posterior of the last
+ * save_gamma E-step, by forward filtering and backward sampling.  Conventions as for the transition products: caller's rows
+ * l = 1 .. L with spans s_l, P_l = s_1 + .. + s_l, positions 0 .. N with N = P_L; position 0 is column 0, row l covers positions
+ * P_{l-1} + 1 .. P_l; a_0 = pi and a_p = e_p o (T^T a_{p-1}), renormalised freely.  Path k:
+ *     x_N is drawn with weights w_i = a_N(i);  for q = N - 1 .. 0, x_q given x_{q+1} = j is drawn with weights w_i = a_q(i) T(i, j).
+ * Every draw is an inverse CDF in ASCENDING state order:  C_i = w_0 + .. + w_i,  x = min{ i : C_i > u C_{M-1} }, clamped to M - 1.
+ * The uniform of the draw of x_q of path k comes from Philox4x32-10 (round multipliers 0xD2511F53, 0xCD9E8D57; key increments
+ * 0x9E3779B9, 0xBB67AE85) with key = (seed & 0xffffffff, seed >> 32) and counter = (q & 0xffffffff, q >> 32, k, contig):
+ *     u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53    from output words w0, w1.
+ * Known answers (counter / key -> output):
+ *     0 0 0 0 / 0 0                                              -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8   (u = 0.39904647231489565)
+ *     ffffffff x 4 / ffffffff x 2                                -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344 / a4093822 299f31d0    -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * Path k of contig c under `seed` is therefore a pure function of the stored vectors, seed, c and k: it does not depend on how many
+ * paths a call asks for, on the window or selection it returns, on how paths are grouped onto wavefronts (SMCPP_PATH_BATCH) or on
+ * what ran before, and a caller can reproduce it on the host from smcpp_get_pi / _transition / _emission_probs.  The device takes
+ * a_q from what the E-step stored: the float alpha at the row's start (a_0: the stored column 0), advanced through the row's
+ * interior by the O(M) scan step and kept as floats, so its CDF agrees with the float64 one to the accuracy of the per-row
+ * posterior (bar 2e-5; tests/test_gpu_posterior_paths.py holds every draw to it); T(i, j) is the manager's transition matrix in fp64; beta is not used.
+ * Preconditions are those of smcpp_posterior_transitions, and: npaths >= 1, path0 >= 0, path0 + npaths <= 2^31,
+ * 0 <= pos0 < pos1 <= P_L + 1, at most 2^31 - 1 output elements per array and call (also npaths x engine rows), at most 1 GiB of
+ * scratch.  Every failure happens before anything is launched.
+ *
+ * smcpp_posterior_sample_rows: per caller's row of the selection range(start, stop, step) over 0 .. L the state at the row's last
+ * position and the number of positions p of the row with x_{p-1} < x_p (up) / x_{p-1} > x_p (down); column 0: the state at
+ * position 0 and (0, 0). */
+int smcpp_posterior_sample_rows(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths,
+                                long long start, long long stop, long long step,
+                                int *state, int *up, int *down /* each [npaths x ncols] row-major or NULL */);
+/* smcpp_posterior_sample_positions: the states at positions pos0 .. pos1 - 1 of 0 .. P_L. */
+int smcpp_posterior_sample_positions(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths,
+                                     long long pos0, long long pos1, int *out /* [npaths x (pos1 - pos0)] row-major */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,33 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_posterior_transition_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
         return out
 
+    def posterior_sample_rows(self, c=0, n_paths=1, seed=0, first_path=0, start=0, stop=None, step=1):
+        """Joint draws of the hidden-state path of contig `c` from the posterior (forward filtering, backward sampling on the device),
+        reduced per row: dict of `state`, `up`, `down`, each int32 `[n_paths, ncols]` over the columns `range(start, stop, step)` -
+        the state at the row's last position and the number of the row's positions at which the sampled path moves to a higher /
+        lower state; column 0 holds the state at position 0 and zeros.  Path `first_path + k` under `seed` is the same whatever
+        else a call asks for (include/smcpp_engine.h: smcpp_posterior_sample_rows states the contract and the random stream)."""
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        args = (self._im, int(c), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_path), int(n_paths), start, stop, step)
+        E.check(E.lib().smcpp_posterior_sample_rows(*args, None, None, None))      # (the checks alone: nothing is allocated for a bad call)
+        ret = {k: np.empty((int(n_paths), ncols), dtype=np.int32) for k in ("state", "up", "down")}
+        E.check(E.lib().smcpp_posterior_sample_rows(*args, E.iptr(ret["state"]), E.iptr(ret["up"]), E.iptr(ret["down"])))
+        return ret
+
+    def posterior_sample_positions(self, c=0, n_paths=1, seed=0, first_path=0, pos0=0, pos1=None):
+        """int32 `[n_paths, pos1 - pos0]`: the states of the sampled paths `first_path .. first_path + n_paths - 1` of contig `c` at
+        positions `pos0 .. pos1 - 1` of `0 .. P_L` (position 0 is column 0, row `l` covers positions `P_{l-1} + 1 .. P_l`;
+        default: all of them)."""
+        c = int(c)
+        if pos1 is None:
+            pos1 = int(self._observations[c][:, 0].sum(dtype=np.int64)) + 1 if 0 <= c < self._num_hmms else 1     # (a bad contig index: the engine raises)
+        pos0, pos1 = int(pos0), int(pos1)
+        args = (self._im, c, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_path), int(n_paths), pos0, pos1)
+        E.check(E.lib().smcpp_posterior_sample_positions(*args, None))             # (the checks alone)
+        out = np.empty((int(n_paths), pos1 - pos0), dtype=np.int32)
+        E.check(E.lib().smcpp_posterior_sample_positions(*args, E.iptr(out)))
+        return out
+
     @property
     def xisums(self):
         ret = []

@@ -111,6 +111,8 @@ cdef extern from "smcpp_engine.h":
     int smcpp_posterior_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
     int smcpp_posterior_transitions(smcpp_im *im, int contig, long long start, long long stop, long long step, double *stay, double *up, double *down) nogil
     int smcpp_posterior_transition_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
+    int smcpp_posterior_sample_rows(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths, long long start, long long stop, long long step, int *state, int *up, int *down) nogil
+    int smcpp_posterior_sample_positions(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths, long long pos0, long long pos1, int *out) nogil
 # --- end generated ---
 
 aca = np.ascontiguousarray
@@ -450,6 +452,42 @@ cdef class _PyInferenceManager:
             rc = smcpp_posterior_transition_windows(self._im, cc, W, &nw, op)
         _check(rc)
         return out[:, :nw] if nw < out.shape[1] else out
+
+    def posterior_sample_rows(self, c=0, n_paths=1, seed=0, first_path=0, start=0, stop=None, step=1):
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        cdef int cc = c, rc
+        cdef unsigned long long sd = int(seed) & 0xFFFFFFFFFFFFFFFF
+        cdef long long a = start, b = stop, st = step, k0 = first_path, nk = n_paths
+        with nogil:
+            rc = smcpp_posterior_sample_rows(self._im, cc, sd, k0, nk, a, b, st, NULL, NULL, NULL)   # (the checks alone)
+        _check(rc)
+        cdef long long n = nk
+        cdef long long cells = n * ncols
+        cdef np.ndarray[int, ndim=1] out = np.empty(3 * max(cells, 1), dtype=np.int32)
+        cdef int *p0 = &out[0]
+        cdef int *p1 = p0 + cells
+        cdef int *p2 = p1 + cells
+        with nogil:
+            rc = smcpp_posterior_sample_rows(self._im, cc, sd, k0, nk, a, b, st, p0, p1, p2)
+        _check(rc)
+        return {k: out[x * cells:(x + 1) * cells].reshape(n, ncols).copy() for x, k in enumerate(("state", "up", "down"))}
+
+    def posterior_sample_positions(self, c=0, n_paths=1, seed=0, first_path=0, pos0=0, pos1=None):
+        cdef int cc = c, rc
+        if pos1 is None:
+            pos1 = int(self._keep[cc][:, 0].sum(dtype=np.int64)) + 1 if 0 <= cc < self._num_hmms else 1
+        cdef unsigned long long sd = int(seed) & 0xFFFFFFFFFFFFFFFF
+        cdef long long a = pos0, b = pos1, k0 = first_path, nk = n_paths
+        with nogil:
+            rc = smcpp_posterior_sample_positions(self._im, cc, sd, k0, nk, a, b, NULL)              # (the checks alone)
+        _check(rc)
+        cdef long long n = nk, w = b - a
+        cdef np.ndarray[int, ndim=1] out = np.empty(max(n * w, 1), dtype=np.int32)
+        cdef int *op = &out[0]
+        with nogil:
+            rc = smcpp_posterior_sample_positions(self._im, cc, sd, k0, nk, a, b, op)
+        _check(rc)
+        return out[:n * w].reshape(n, w).copy()
 
     property xisums:
         def __get__(self):

@@ -40,6 +40,7 @@
 #include "jcsfs.hpp"
 #include "posterior_dev.hpp"    // products of the per-row posteriors: columns, per-column summaries, windows
 #include "posterior_trans_dev.hpp"   // posterior transition products: stay / up / down per row and per window
+#include "posterior_paths_dev.hpp"   // posterior paths: forward filtering, backward sampling (state / up / down per row, per position)
 
 // The engine is one translation unit in seven parts (each part sees everything above it):
 #include "engine_base.hpp"        // logging, pinned arena, device buffers, the device route of the cold preparation (DevPrep, TwoPopDevCsfs)

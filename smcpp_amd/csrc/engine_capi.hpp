@@ -577,6 +577,134 @@ int smcpp_posterior_transition_windows(smcpp_im *im, int c, long long window_bp,
     API_END
 }
 
+// ---- posterior paths (posterior_paths_dev.hpp) ----
+static void post_paths_check(long long path0, long long npaths) {
+    if (npaths < 1) throw std::runtime_error("posterior paths: n_paths < 1");
+    if (path0 < 0) throw std::runtime_error("posterior paths: first_path < 0");
+    if (path0 > (1LL << 31) || npaths > (1LL << 31) || path0 + npaths > (1LL << 31))
+        throw std::runtime_error("posterior paths: first_path + n_paths > 2^31 (the path index is one 32-bit word of the counter)");
+}
+static void post_paths_cap(long long npaths, long long per_path, const char *what) {
+    if (npaths > ((1LL << 31) - 1) / std::max<long long>(1, per_path))
+        throw std::runtime_error(std::string("posterior paths: ") + what + " (" + std::to_string(npaths) + " paths x " +
+                                 std::to_string(per_path) + ") exceed the cap of 2^31 - 1 elements per call: ask for fewer paths "
+                                 "or a narrower window");
+}
+
+// The arguments have been checked (post_need_gamma, post_transitions_check, post_paths_check, the caps); ncols == 0: no per-row
+// product, pos1 <= pos0: no per-position product.
+smcpp_im::PostPaths smcpp_im::post_paths(int c, unsigned long long seed, long long path0, long long npaths, long long start,
+                                         long long step, long long ncols, long long pos0, long long pos1) {
+    HIPCHK(hipSetDevice(device));
+    const int MS = 64 * NPL, Le = Ls[c];
+    const bool want_rows = ncols > 0, want_pos = pos1 > pos0;
+    int smax = 1;                                      // the contig's longest engine row
+    for (int i = 1; i <= Le; ++i) {
+        const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+        if (ri.gid >= 0) smax = std::max(smax, groups[ri.gid].span);
+    }
+    PpArgs pa;
+    pa.nck = (smax + PP_BLK - 1) / PP_BLK - 1;
+    // paths per wavefront: as few as fill the wavefront slots (a batch shares the forward walk, but its paths run one behind the other)
+    const long long slots = NPL >= 8 ? 1024 : 4096;
+    long long batch = opt().has(smcpp_opt::O_PATH_BATCH) ? opt().ll(smcpp_opt::O_PATH_BATCH, 1) : (npaths + slots - 1) / slots;
+    batch = std::max<long long>(1, std::min<long long>(64, batch));
+    const long long nbatches = (npaths + batch - 1) / batch;
+    // scratch per wavefront: one block of parked vectors + the checkpoints of the longest row; at most 1 GiB in all
+    const size_t per_wave = (size_t)PP_BLK * MS * sizeof(float) + (size_t)pa.nck * MS * sizeof(double);
+    if (per_wave > (1ull << 30))
+        throw std::runtime_error("posterior paths: the checkpoints of a row of " + std::to_string(smax) + " positions exceed the scratch "
+                                 "cap of 1 GiB");
+    const int nw = (int)std::max<long long>(1, std::min<long long>(std::min(nbatches, slots), (long long)((1ull << 30) / per_wave)));
+    const int *first = want_rows ? piece_first_dev(c) : nullptr;
+    ensure_T();
+    if ((int)T.size() != M * M) throw std::runtime_error("posterior paths: the transition matrix is missing");
+    std::vector<double> TT((size_t)(M + 1) * MS, 0.0);
+    for (int j = 0; j < M; ++j)
+        for (int i = 0; i < M; ++i) TT[(size_t)j * MS + i] = T[(size_t)i * M + j];
+    for (int i = 0; i < M; ++i) TT[(size_t)M * MS + i] = 1.0;
+    d_pp_TT.upload(TT, stream);
+    d_pt_gen.upload(ss_gen, stream);                   // (ss_gen is a member: it outlives the copy)
+    SsArgs sa = SsArgs();
+    sa.M = M; sa.Mp = Mp;
+    const double *gd = d_pt_gen.p;
+    sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
+    sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
+    sa.c0 = ss_c0;
+    pa.M = M; pa.Mp = Mp; pa.L = Le; pa.base = contig_base[c];
+    d_pp_park.alloc((size_t)nw * PP_BLK * MS);
+    d_pp_ckpt.alloc(std::max<size_t>(1, (size_t)nw * pa.nck * MS));
+    if (want_rows) d_pp_eng.alloc((size_t)3 * npaths * (Le + 1));
+    if (want_pos) d_pp_pos.alloc((size_t)npaths * (pos1 - pos0));
+    pa.rowinfo = d_rowinfo.p; pa.g_span = d_g_span.p; pa.E = d_E.p; pa.alpha = d_alpha.p; pa.TT = d_pp_TT.p;
+    pa.park = d_pp_park.p; pa.ckpt = d_pp_ckpt.p;
+    pa.k0 = (unsigned)(seed & 0xffffffffull); pa.k1 = (unsigned)(seed >> 32); pa.contig = (unsigned)c;
+    pa.path0 = path0; pa.npaths = npaths; pa.nbatches = nbatches; pa.batch = (int)batch;
+    pa.N = user_prefix[c][user_Ls[c]];
+    pa.pos0 = want_pos ? pos0 : 0; pa.pos1 = want_pos ? pos1 : 0;
+    pa.pos_out = want_pos ? d_pp_pos.p : nullptr;
+    pa.rows_out = want_rows ? d_pp_eng.p : nullptr;
+    pp_batch = (int)batch;
+    const dim3 grid(ceil_div(nw, 4)), block(256);
+    switch (NPL) {
+#define PP_(x) case x: hipLaunchKernelGGL((k_post_paths<x>), grid, block, 0, stream, sa, pa, nw); break;
+        PP_(1) PP_(2) PP_(3) PP_(4) PP_(8)
+        default: PP_(16)
+#undef PP_
+    }
+    HIPCHK(hipGetLastError());
+    PostPaths r = {nullptr, want_pos ? d_pp_pos.p : nullptr};
+    if (want_rows) {
+        PostSel sel;
+        sel.start = start; sel.step = step; sel.ncols = ncols;
+        d_pp_sel.alloc((size_t)3 * npaths * ncols);
+        hipLaunchKernelGGL(k_post_paths_select, dim3((unsigned)ceil_div(npaths * ncols, 256)), dim3(256), 0, stream, sel, (long long)Le,
+                           npaths, first, (const int *)d_pp_eng.p, d_pp_sel.p);
+        HIPCHK(hipGetLastError());
+        r.rows = d_pp_sel.p;
+    }
+    HIPCHK(hipStreamSynchronize(stream));              // (TT is a local: the copy has to be done before it goes)
+    return r;
+}
+
+int smcpp_posterior_sample_rows(smcpp_im *im, int c, unsigned long long seed, long long path0, long long npaths, long long start,
+                                long long stop, long long step, int *state, int *up, int *down) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    const long long ncols = post_check_selection(im, c, start, stop, step);
+    im->post_transitions_check();
+    post_paths_check(path0, npaths);
+    post_paths_cap(npaths, ncols, "the outputs");
+    post_paths_cap(npaths, (long long)im->Ls[c] + 1, "the per-row products over the engine's rows");
+    if (!state && !up && !down) return 0;
+    const smcpp_im::PostPaths r = im->post_paths(c, seed, path0, npaths, start, step, ncols, 0, 0);
+    hipStream_t s = im->stream;
+    int *dst[3] = {state, up, down};
+    const size_t cells = (size_t)npaths * ncols;
+    for (int x = 0; x < 3; ++x)
+        if (dst[x]) HIPCHK(hipMemcpyAsync(dst[x], r.rows + (size_t)x * cells, sizeof(int) * cells, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
+int smcpp_posterior_sample_positions(smcpp_im *im, int c, unsigned long long seed, long long path0, long long npaths, long long pos0,
+                                     long long pos1, int *out) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    im->post_transitions_check();
+    post_paths_check(path0, npaths);
+    const long long N = im->user_prefix[c][im->user_Ls[c]];
+    if (pos0 < 0) throw std::runtime_error("posterior paths: pos0 < 0");
+    if (pos1 > N + 1) throw std::runtime_error("posterior paths: pos1 > P_L + 1 (the contig has " + std::to_string(N + 1) + " positions)");
+    if (pos0 >= pos1) throw std::runtime_error("posterior paths: empty window of positions (pos0 >= pos1)");
+    post_paths_cap(npaths, pos1 - pos0, "the outputs");
+    if (!out) return 0;
+    const smcpp_im::PostPaths r = im->post_paths(c, seed, path0, npaths, 0, 1, 0, pos0, pos1);
+    HIPCHK(hipMemcpyAsync(out, r.pos, sizeof(int) * (size_t)npaths * (pos1 - pos0), hipMemcpyDeviceToHost, im->stream));
+    HIPCHK(hipStreamSynchronize(im->stream));
+    API_END
+}
+
 int smcpp_gamma_cols(smcpp_im *im, int c) {
     if (c < 0 || c >= im->n_contigs) return -1;
     return im->gamma_valid ? im->user_Ls[c] + 1 : 1;

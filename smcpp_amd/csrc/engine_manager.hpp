@@ -213,6 +213,17 @@ struct smcpp_im {
     const int *piece_first_dev(int c);            // first piece of every caller's row of contig c on the device; nullptr: no row is cut
     void post_transitions_check();                // throws unless the stored vectors and a structured T are there
     const double *post_transitions(int c, long long start, long long step, long long ncols);   // -> [3][ncols] on the device
+    // posterior paths (posterior_paths_dev.hpp, smcpp_posterior_sample_*): the transposed dense T, the wavefronts' scratch (parked
+    // forward vectors of a block, checkpoints of long rows), state / up / down per path and engine row, per selected caller's row,
+    // and the states per path and position of a window
+    DevBuf<double> d_pp_TT, d_pp_ckpt;
+    DevBuf<float> d_pp_park;
+    DevBuf<int> d_pp_eng, d_pp_sel, d_pp_pos;
+    int pp_batch = 0;                             // paths per wavefront of the last call (smcpp_describe)
+    struct PostPaths { const int *rows, *pos; };
+    // rows: [3][npaths][ncols] of the selection (ncols > 0), pos: [npaths][pos1 - pos0] (pos1 > pos0), on the device, on `stream`
+    PostPaths post_paths(int c, unsigned long long seed, long long path0, long long npaths, long long start, long long step,
+                         long long ncols, long long pos0, long long pos1);
     // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;

@@ -253,6 +253,8 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
         static const char *const route[] = {"none", "device", "host"};
         s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";
+        // paths per wavefront of the last posterior path call (0: none yet)
+        s += ", \"path_batch\": " + std::to_string(im->pp_batch);
     }
     s += "}";
     if (buf && cap > 0) {

@@ -103,7 +103,8 @@ def average_coal_times(model, hidden_states):
 
 
 def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
-                       start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False, transitions=False):
+                       start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False, transitions=False,
+                       paths=0, seed=0):
     """What a posterior decoding is reduced to, computed on the device without ever fetching the `[M, L+1]` matrix (arguments and
     set-up as `posterior`: hidden states, the prepended missing row, `start` / `end` / `thinning`, one or two populations).
     Returns `(hidden_states, products)`; `products[c]` is a dict for contig c:
@@ -122,6 +123,11 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
                             (`im.posterior_transitions`);
       `transition_windows`  only with `window=W`: `[3, ceil(P / W)]`, the same counts per window of W base pairs, a row
                             apportioned uniformly over its base pairs (windows as for `windows`).
+    With `paths=K > 0` each dict gains joint draws of the hidden-state path from the posterior, reduced per column
+    (`im.posterior_sample_rows(c, K, seed)`; path k of contig c under `seed` is the same whatever K is):
+      `path_state`  `[K, L+1]` int32: the state of sampled path k at the row's last position (column 0: at position 0);
+      `path_up`, `path_down`  `[K, L+1]` int32: the number of the row's positions at which path k moves to a higher (older) / lower
+                    state; `(path_up + path_down).sum(axis=1)` is the number of breakpoints of path k.
     `return_manager=True` appends the inference manager."""
     hs, obs, im = _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end,
                                 thinning)
@@ -138,6 +144,9 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
             prod["transitions"] = np.stack([tr["stay"], tr["up"], tr["down"]])
             if window is not None:
                 prod["transition_windows"] = im.posterior_transition_windows(c, window)
+        if paths > 0:
+            pr = im.posterior_sample_rows(c, n_paths=paths, seed=seed)
+            prod["path_state"], prod["path_up"], prod["path_down"] = pr["state"], pr["up"], pr["down"]
         products.append(prod)
     if return_manager:
         return hs, products, im
@@ -155,10 +164,12 @@ def save_npz(path, hs, gammas, sites, names):
 
 def save_products_npz(path, hs, products, names):
     """`.npz` of `posterior_products`: `hidden_states` and per file `<file>_sites`, `<file>_path`, `<file>_mean_tmrca`,
-    `<file>_qstate` and, where they were asked for, `<file>_windows`, `<file>_transitions`, `<file>_transition_windows`."""
+    `<file>_qstate` and, where they were asked for, `<file>_windows`, `<file>_transitions`, `<file>_transition_windows`,
+    `<file>_path_state`, `<file>_path_up`, `<file>_path_down`."""
     out = {"hidden_states": hs}
     for nm, prod in zip(names, products):
-        for key in ("sites", "path", "mean_tmrca", "qstate", "windows", "transitions", "transition_windows"):
+        for key in ("sites", "path", "mean_tmrca", "qstate", "windows", "transitions", "transition_windows", "path_state", "path_up",
+                    "path_down"):
             if key in prod:
                 out[f"{nm}_{key}"] = prod[key]
     np.savez_compressed(path, **out)
