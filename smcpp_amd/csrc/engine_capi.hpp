@@ -517,6 +517,7 @@ const double *smcpp_im::post_transitions(int c, long long start, long long step,
     d_pt_eng.alloc((size_t)3 * (Le + 1));
     pa.rowinfo = d_rowinfo.p; pa.g_span = d_g_span.p; pa.E = d_E.p; pa.alpha = d_alpha.p; pa.beta = d_beta.p;
     pa.park = d_pt_park.p; pa.ckpt = d_pt_ckpt.p; pa.out = d_pt_eng.p;
+    pt_waves = nw;
     const dim3 grid(ceil_div(nw, 4)), block(256);
     switch (NPL) {
 #define PT_(x) case x: hipLaunchKernelGGL((k_post_transitions<x>), grid, block, 0, stream, sa, pa, nw); break;
@@ -644,7 +645,7 @@ smcpp_im::PostPaths smcpp_im::post_paths(int c, unsigned long long seed, long lo
     pa.pos0 = want_pos ? pos0 : 0; pa.pos1 = want_pos ? pos1 : 0;
     pa.pos_out = want_pos ? d_pp_pos.p : nullptr;
     pa.rows_out = want_rows ? d_pp_eng.p : nullptr;
-    pp_batch = (int)batch;
+    pp_batch = (int)batch; pp_batches = nbatches; pp_waves = nw;
     const dim3 grid(ceil_div(nw, 4)), block(256);
     switch (NPL) {
 #define PP_(x) case x: hipLaunchKernelGGL((k_post_paths<x>), grid, block, 0, stream, sa, pa, nw); break;

@@ -220,6 +220,8 @@ struct smcpp_im {
     DevBuf<float> d_pp_park;
     DevBuf<int> d_pp_eng, d_pp_sel, d_pp_pos;
     int pp_batch = 0;                             // paths per wavefront of the last call (smcpp_describe)
+    long long pp_batches = 0;                     // batches of the last call
+    int pp_waves = 0, pt_waves = 0;               // wavefronts launched by the last path / transition call (smcpp_describe)
     struct PostPaths { const int *rows, *pos; };
     // rows: [3][npaths][ncols] of the selection (ncols > 0), pos: [npaths][pos1 - pos0] (pos1 > pos0), on the device, on `stream`
     PostPaths post_paths(int c, unsigned long long seed, long long path0, long long npaths, long long start, long long step,

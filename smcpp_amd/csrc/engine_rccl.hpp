@@ -253,8 +253,10 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
         static const char *const route[] = {"none", "device", "host"};
         s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";
-        // paths per wavefront of the last posterior path call (0: none yet)
-        s += ", \"path_batch\": " + std::to_string(im->pp_batch);
+        // the launch shape of the last posterior path call - paths per wavefront, batches, wavefronts - and the wavefronts of the
+        // last posterior transition call (0: none yet); a wavefront takes more than one batch / row where there are fewer of them
+        s += ", \"path_batch\": " + std::to_string(im->pp_batch) + ", \"path_batches\": " + std::to_string(im->pp_batches);
+        s += ", \"path_waves\": " + std::to_string(im->pp_waves) + ", \"transition_waves\": " + std::to_string(im->pt_waves);
     }
     s += "}";
     if (buf && cap > 0) {

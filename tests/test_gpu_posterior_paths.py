@@ -30,7 +30,33 @@ No u of these 1.6e6 draws lay between the device's CDF and the oracle's: with th
 from the same vectors miss theirs, about one draw in 1e7 .. 1e5 is expected to (two edges per draw).  State frequencies of 4096 paths
 at 739 positions: worst deviation 0.49 of the bound, the oracle's sampler 0.49 as well; mean up / down totals of 1024 paths 0.19 /
 0.22 standard errors from the expected counts; the states at the row ends 0.43 of the bound.
+
+The launch shape.  The kernel is persistent: wavefront gw owns one slice of scratch (the parked vectors of a block of 64 positions,
+the fp64 checkpoints of a long row) and takes batches gw, gw + nwaves, ..; the host gives it the fewest of the batches, 4096 slots
+(1024 from 8 states per lane) and the wavefronts whose scratch fits 1 GiB.  The cases below assert from `describe()` (`path_batch`,
+`path_batches`, `path_waves`, the plan) that they reach the branch they are named for, and hold every bit-equality between a call
+in which wavefronts take a second batch and calls of at most 64 paths, in which none does:
+
+  case                                      launch (batches x paths on wavefronts)   worst distance   draws off   draws held
+  long rows M = 65 / 150 / 256 (4 paths;    4 x 1 on 4; rows of 16 blocks at         0                0           157 588 each
+    SMCPP_SPLIT_SPANS=0)                      2 / 3 / 4 states per lane
+  scan:M300, 1030 paths, batch 1            1030 x 1 on 1024 (8 states per lane)     0                0           19 320
+    the same without the switch             515 x 2 on 515                           (the same bits)
+  freq:M64, 4100 paths, batch 1             4100 x 1 on 4096                         0                0           17 736
+  scratch cap: M = 256, a row of 10^5       340 x 1 on 328 (3 264 512 bytes of       0                0           1 400 028
+    positions, 340 paths, default switches    scratch per wavefront)
+  scan:M64 / cut:M100, 130 paths, batch 64  3 x (64, 64, 2) on 3                     0                0           49 512 / 162 584
+  cut:M100 / long rows M = 65, 8 paths,     2 x (7, 1) on 2: windows and selections  (slices of the full results of batch 1)
+    batch 7
+
+(draws held: those of the paths handed to the oracle - paths 0 .. 7 and the last 16, which include every path of a second batch;
+paths 326 .. 339; paths 60 .. 67 across the seam of two full batches.)  Wall time on one MI355X: every case below 1.5 s but the
+scratch cap: its call for the positions of the 340 paths takes 0.16 s (two walks of 10^5 positions behind each other on 12
+wavefronts, 136 MB copied to the host), the call for the per-row product 0.15 s, the six calls of 64 paths about as much each;
+the test takes 4.5 s, most of it the oracle's 10^5 positions at 256 states.
 """
+import time
+
 import numpy as np
 import pytest
 
@@ -211,6 +237,212 @@ def test_identical_contigs_get_different_paths(engine_opt):
     for c, pr in enumerate((a, b)):
         assert pathref.draw_margins(*model, ob, SEED, c, 0, pr["pos"]).max() <= GAMMA_TOL
     assert pathref.draw_margins(*model, ob, SEED, 0, 0, b["pos"]).max() > GAMMA_TOL      # (contig 1's paths are not contig 0's)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the launch shape: multi-block rows beyond one state per lane, a wavefront's second batch, full batches, windows under batching
+# ---------------------------------------------------------------------------------------------------------------------------------
+_LONG = {}
+
+
+def launch(im, label):
+    """(paths per batch, batches, wavefronts) of the last path call, printed."""
+    d = im.describe()
+    got = d["path_batch"], d["path_batches"], d["path_waves"]
+    print(f"{label}: launch {got[1]} batches of {got[0]} paths on {got[2]} wavefronts")
+    return got
+
+
+def long_rows_manager(M, engine_opt):
+    """Un-cut un-binned rows of 64 / 65 / 128 / 129 / 1000 positions (16 blocks, 15 checkpoints, a ragged last block) at
+    2 .. 4 states per lane (SMCPP_SPLIT_SPANS=0); contigs of 160, 132, 1 and 2 rows."""
+    if "c" not in _LONG:
+        _LONG["c"] = tg.unbinned_contigs(120, spans=(64, 65, 128, 129, 1000), cap=1000)
+    contigs = _LONG["c"]
+    assert [len(ob) for ob in contigs] == [160, 132, 1, 2]
+    assert [int(ob[:, 0].sum()) for ob in contigs] == [21_666, 16_725, 1, 1001]
+    assert all(int(ob[:, 0].max()) == 1000 for ob in (contigs[0], contigs[1], contigs[3]))
+    engine_opt("SMCPP_SPLIT_SPANS", "0")
+    im = tg._onepop(M, contigs, tg.TH_U, tg.RH_U)
+    im.save_gamma = True
+    im.E_step()
+    plan = im.describe()["plan"]
+    print(f"long rows, M = {M}: plan { {k: plan[k] for k in ('per_row_gamma', 'states_per_lane', 'long_rows_cut', 'chain_family')} }")
+    assert plan["states_per_lane"] == (M + 63) // 64 and not plan["long_rows_cut"], plan
+    return im, contigs
+
+
+def in_calls(im, c, K, size=64):
+    """Paths 0 .. K - 1 of both products fetched in calls of at most `size` paths, none of which gives a wavefront a second batch."""
+    pos, rws = [], []
+    for k0 in range(0, K, size):
+        n = min(size, K - k0)
+        pos.append(im.posterior_sample_positions(c, n, SEED, k0))
+        d = im.describe()
+        assert d["path_batches"] <= d["path_waves"], d
+        rws.append(rows(im, c, n, SEED, k0))
+        d = im.describe()
+        assert d["path_batches"] <= d["path_waves"], d
+    return {"rows": np.concatenate(rws, axis=1), "pos": np.concatenate(pos, axis=0)}
+
+
+def check_margins(model, ob, c, k0, pos, label):
+    """Every draw of the given paths (path k0 + i in line i) within GAMMA_TOL of the oracle's CDF; -> (worst, off, draws)."""
+    m = pathref.draw_margins(*model, ob, SEED, c, k0, pos)
+    assert np.all(np.isfinite(m))
+    print(f"{label}: paths {k0} .. {k0 + len(pos) - 1}, worst distance {m.max():.2e}, {int((m > 0).sum())} of {m.size} draws off")
+    bad = np.argwhere(m > GAMMA_TOL)
+    assert len(bad) == 0, f"{label}: {len(bad)} draws further than {GAMMA_TOL} from the oracle's CDF, e.g. (path - {k0}, position) " \
+                          f"{bad[:8].tolist()}: {m[tuple(bad[:8].T)]}"
+    return float(m.max()), int((m > 0).sum()), m.size
+
+
+@pytest.mark.parametrize("M", [65, 150, 256])
+def test_multi_block_rows_beyond_one_state_per_lane(engine_opt, M):
+    """Rows of up to 16 blocks at 2, 3 and 4 states per lane (the checkpoints ckpt[(b - 1) MS + lane NPL + k], the ragged last
+    block): every draw of 4 paths of every contig against the oracle, the per-row product, the position windows."""
+    im, contigs = long_rows_manager(M, engine_opt)
+    model = hmm(im)
+    K = 4
+    worst, off, draws = 0.0, 0, 0
+    for c, ob in enumerate(contigs):
+        label = f"long rows M = {M} contig {c}"
+        spans = ob[:, 0]
+        N = int(spans.sum())
+        pos = im.posterior_sample_positions(c, K, SEED)
+        assert launch(im, label) == (1, K, K)
+        assert pos.shape == (K, N + 1) and pos.dtype == np.int32
+        assert pos.min() >= 0 and pos.max() < M, (label, pos.min(), pos.max())
+        w = check_margins(model, ob, c, 0, pos, label)
+        worst, off, draws = max(worst, w[0]), off + w[1], draws + w[2]
+        v = rows(im, c, K, SEED)
+        want = np.stack(pathref.rows_from_positions(pos, spans))
+        assert v.shape == (3, K, len(ob) + 1) and np.array_equal(v, want), (label, np.argwhere(v != want)[:8].tolist())
+        for p0, p1 in position_windows(spans):
+            got = im.posterior_sample_positions(c, K, SEED, 0, p0, p1)
+            assert got.shape == (K, p1 - p0) and np.array_equal(got, pos[:, p0:p1]), (label, p0, p1, N)
+    print(f"long rows M = {M}: WORST distance {worst:.2e}, {off} draws off of {draws}")
+
+
+@pytest.mark.parametrize("case", ["scan:M300", "freq:M64"])
+def test_second_batch_by_slots(engine_opt, freq, case):
+    """More batches of one path than wavefront slots (1030 on 1024 at 8 states per lane, 4100 on 4096 at one): the wavefronts that
+    take a second batch start it from a fresh state on scratch the first has used.  Both products have the bits of the same
+    paths fetched in calls of 64 (which never stride); every draw of paths 0 .. 7 and of the last 16 - every path of a second
+    batch among them - against the oracle.  M = 300 without the switch: batches of 2 paths, the same bits."""
+    if case == "freq:M64":
+        im, contigs, K, slots, npl = freq["im"], [freq["ob"]], 4100, 4096, 1
+    else:
+        (im, contigs), K, slots, npl = tg.run_case(case, engine_opt), 1030, 1024, 8
+        assert [int(ob[:, 0].sum()) for ob in contigs] == [736, 1, 65]
+    assert im.describe()["plan"]["states_per_lane"] == npl
+    model = hmm(im)
+    for c, ob in enumerate(contigs):
+        label = f"{case} contig {c}"
+        engine_opt("SMCPP_PATH_BATCH", "1")
+        pos = im.posterior_sample_positions(c, K, SEED)
+        shape = launch(im, label + " positions")
+        assert shape == (1, K, slots) and shape[1] > shape[2], shape
+        v = rows(im, c, K, SEED)
+        shape = launch(im, label + " rows")
+        assert shape == (1, K, slots) and shape[1] > shape[2], shape
+        same_bits({"rows": v, "pos": pos}, in_calls(im, c, K))
+        assert pos.min() >= 0 and pos.max() < im.M
+        check_margins(model, ob, c, 0, pos[:8], label)
+        check_margins(model, ob, c, K - 16, pos[K - 16:], label)
+        assert np.array_equal(v, np.stack(pathref.rows_from_positions(pos, ob[:, 0]))), label
+        if npl == 8:
+            # the host's own choice above one path per wavefront
+            engine_opt("SMCPP_PATH_BATCH", None)
+            two = {"pos": im.posterior_sample_positions(c, K, SEED)}
+            assert launch(im, label + " default batching") == (2, K // 2, K // 2)
+            two["rows"] = rows(im, c, K, SEED)
+            assert launch(im, label + " default batching") == (2, K // 2, K // 2)
+            same_bits(two, {"rows": v, "pos": pos})
+
+
+def test_second_batch_by_the_scratch_cap(engine_opt):
+    """Default switches, M = 256, an un-cut row of 10^5 positions: 64 256 4 + 1562 256 8 = 3 264 512 bytes of scratch per wavefront,
+    328 wavefronts in 1 GiB, 340 paths of a batch each - 12 wavefronts walk the row a second time over the checkpoints and parked
+    vectors of their first path.  The bits of calls of 64 paths; every draw of paths 326 .. 339 against the oracle."""
+    engine_opt("SMCPP_PATH_BATCH", None)
+    engine_opt("SMCPP_SPLIT_SPANS", None)
+    contigs, theta, rho = tg.case_inputs("unbinned", 256)
+    im = tg._onepop(256, contigs, theta, rho)
+    im.save_gamma = True
+    im.E_step()
+    plan = im.describe()["plan"]
+    assert plan["states_per_lane"] == 4 and not plan["long_rows_cut"], plan
+    c, K = 3, 340
+    ob = contigs[c]
+    assert ob[:, 0].tolist() == [100_000, 1]
+    waves = (1 << 30) // (64 * 256 * 4 + 1562 * 256 * 8)
+    assert waves == 328
+    t0 = time.perf_counter()
+    pos = im.posterior_sample_positions(c, K, SEED)
+    t1 = time.perf_counter()
+    shape = launch(im, f"scratch cap, positions ({t1 - t0:.3f} s)")
+    assert shape == (1, K, waves) and shape[1] > shape[2], shape
+    assert pos.shape == (K, 100_002) and pos.min() >= 0 and pos.max() < 256
+    t0 = time.perf_counter()
+    v = rows(im, c, K, SEED)
+    t1 = time.perf_counter()
+    shape = launch(im, f"scratch cap, rows ({t1 - t0:.3f} s)")
+    assert shape == (1, K, waves) and shape[1] > shape[2], shape
+    same_bits({"rows": v, "pos": pos}, in_calls(im, c, K))
+    assert np.array_equal(v, np.stack(pathref.rows_from_positions(pos, ob[:, 0])))
+    check_margins(hmm(im), ob, c, 326, pos[326:], "scratch cap")
+
+
+@pytest.mark.parametrize("case", ["scan:M64", "cut:M100"])
+def test_full_and_ragged_batches(engine_opt, case):
+    """130 paths in batches of 64, 64 and 2: every lane of a wavefront carries a path.  The bits of one path per wavefront; every
+    draw of paths 60 .. 67 against the oracle."""
+    im, contigs = manager(case, engine_opt)
+    model = hmm(im)
+    K = 130
+    for c, ob in enumerate(contigs):
+        label = f"{case} contig {c}"
+        engine_opt("SMCPP_PATH_BATCH", "64")
+        full = {"pos": im.posterior_sample_positions(c, K, SEED)}
+        assert launch(im, label + " positions") == (64, 3, 3)
+        full["rows"] = rows(im, c, K, SEED)
+        assert launch(im, label + " rows") == (64, 3, 3)
+        engine_opt("SMCPP_PATH_BATCH", "1")
+        one = {"pos": im.posterior_sample_positions(c, K, SEED)}
+        assert launch(im, label + " one path per wavefront") == (1, K, K)
+        one["rows"] = rows(im, c, K, SEED)
+        assert launch(im, label + " one path per wavefront") == (1, K, K)
+        same_bits(full, one)
+        assert full["pos"].min() >= 0 and full["pos"].max() < im.M
+        check_margins(model, ob, c, 60, full["pos"][60:68], label)
+        assert np.array_equal(full["rows"], np.stack(pathref.rows_from_positions(full["pos"], ob[:, 0]))), label
+
+
+@pytest.mark.parametrize("case", ["cut:M100", "long:M65"])
+def test_windows_and_selections_under_batching(engine_opt, case):
+    """8 paths in batches of 7 and 1: the early exits of a window of positions (the rows and blocks below it, the skipped column
+    0) and the column selections are slices of the full results of one path per wavefront."""
+    engine_opt("SMCPP_PATH_BATCH", None)
+    im, contigs = long_rows_manager(65, engine_opt) if case == "long:M65" else manager(case, engine_opt)
+    K = 8
+    for c, ob in enumerate(contigs):
+        label = f"{case} contig {c}"
+        spans, L = ob[:, 0], len(ob)
+        N = int(spans.sum())
+        engine_opt("SMCPP_PATH_BATCH", None)
+        pos = im.posterior_sample_positions(c, K, SEED)
+        assert launch(im, label + " full") == (1, K, K)
+        v = rows(im, c, K, SEED)
+        engine_opt("SMCPP_PATH_BATCH", "7")
+        for start, stop, step in _selections(L):
+            got = rows(im, c, K, SEED, 0, start, stop, step)
+            assert np.array_equal(got, v[:, :, slice(start, stop, step)]), (label, start, stop, step)
+        assert launch(im, label + " selections") == (7, 2, 2)
+        for p0, p1 in position_windows(spans):
+            got = im.posterior_sample_positions(c, K, SEED, 0, p0, p1)
+            assert got.shape == (K, p1 - p0) and np.array_equal(got, pos[:, p0:p1]), (label, p0, p1, N)
+        assert launch(im, label + " windows") == (7, 2, 2)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

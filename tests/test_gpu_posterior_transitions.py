@@ -39,6 +39,22 @@ against the span / sum over the rows against the engine's xisum):
   eig_b:M13            9.6e-09       6.1e-07        2.2e-16       9.0e-09   (SMCPP_GAMMA_SCAN=0)
   pieces:M65           7.8e-10       3.3e-07        2.2e-16       3.5e-08   (SMCPP_SPLIT_SPANS=0, dense chains)
   dense:M64            7.0e-09       3.3e-07        3.0e-16       3.2e-08   (SMCPP_SS=0)
+
+More rows than wavefronts.  The kernel is persistent: wavefront gw owns one slice of scratch (the parked addends of a block, the
+fp64 checkpoints of a long row) and takes rows 1 + gw, 1 + gw + nwaves, ..; the host gives it the fewest of the rows, 4096 slots
+(1024 from 8 states per lane) and the wavefronts whose scratch fits 1 GiB.  The `stride:` cases assert from `describe()`
+(`transition_waves`, the plan) that the first contig has more rows than wavefronts, check every column, the sums over the rows and
+the windows of 100 base pairs as above, and ask for the same bits on repetition, after the other posterior products and on
+poisoned allocations (wall time of the test with the oracle, of which the device's calls are a few ms):
+
+  case          rows on wavefronts (scratch each)              of the span   large values   sum vs span   rows vs xisum   time
+  stride:M64    1442 on 1264 (848 896 bytes: the 1 GiB cap;    5.6e-08       4.0e-07        2.2e-16       1.5e-08         38 s
+                543 rows of 2 .. 1563 blocks, default plan)
+  stride:M100   4274 on 4096 (98 304 bytes, 2 states a lane)   4.2e-09       1.6e-07        3.3e-16       4.4e-09         0.8 s
+  stride:M300   1235 on 1024 (393 216 bytes, 8 states a lane)  1.6e-08       9.2e-08        2.2e-16       4.3e-09         1.7 s
+  stride:M520   1235 on 1024 (786 432 bytes, 16 states a lane) 5.5e-09       1.1e-07        2.2e-16       3.1e-09         6.2 s
+
+(stride:M64 walks 3.0e5 positions in the oracle, as unbinned:M64 walks 3.4e5 in 58 s.)
 """
 import numpy as np
 import pytest
@@ -300,6 +316,132 @@ def test_poisoned_allocations(engine_opt, case):
     del im
     engine_opt("SMCPP_DEBUG_POISON", None)
     for a, b in zip(clean, poisoned):
+        same_bits(b, a)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# more rows than wavefronts: a wavefront's second row
+# ---------------------------------------------------------------------------------------------------------------------------------
+# case -> (states, states per lane, wavefront slots, rows / positions of the first contig)
+STRIDE = {"stride:M64": (64, 1, 4096, 1442, 199_056), "stride:M100": (100, 2, 4096, 4274, 18_128),
+          "stride:M300": (300, 8, 1024, 1235, 5136), "stride:M520": (520, 16, 1024, 1235, 5136)}
+_STRIDE = {}
+
+
+def stride_inputs(case):
+    """-> (contigs, theta, rho).  stride:M64: un-binned rows of at most 200 positions beside 64 / 65 / 128 / 129 / 10^5 placed by
+    hand - 848 896 bytes of scratch per wavefront, so the 1 GiB cap, not the rows or the slots, sets the wavefront count; the
+    others: more binned rows than slots."""
+    key = "M64" if case == "stride:M64" else "M100" if case == "stride:M100" else "M300"
+    if key not in _STRIDE:
+        _STRIDE[key] = (tg.unbinned_contigs(1400, seeds=(11,), cap=200), tg.TH_U, tg.RH_U) if key == "M64" else \
+                       (tg.binned_contigs(140, 1_800_000), tg.TH_B, tg.RH_B) if key == "M100" else \
+                       (tg.binned_contigs(340, 500_000), tg.TH_B, tg.RH_B)
+    return _STRIDE[key]
+
+
+def stride_manager(case, engine_opt):
+    """An own manager under default switches after a save_gamma E-step, its plan asserted."""
+    engine_opt("SMCPP_SPLIT_SPANS", None)
+    M, npl, slots, L, N = STRIDE[case]
+    contigs, theta, rho = stride_inputs(case)
+    assert (len(contigs[0]), int(contigs[0][:, 0].sum())) == (L, N), (case, len(contigs[0]), int(contigs[0][:, 0].sum()))
+    im = tg._onepop(M, contigs, theta, rho)
+    im.save_gamma = True
+    im.E_step()
+    plan = im.describe()["plan"]
+    print(f"{case}: plan { {k: plan[k] for k in ('per_row_gamma', 'states_per_lane', 'long_rows_cut', 'chain_family')} }")
+    assert plan["states_per_lane"] == npl and not plan["long_rows_cut"], plan
+    if case == "stride:M64":
+        assert plan["chain_family"] == 6, plan
+    return im, contigs
+
+
+def stride_waves(case, ob):
+    """The wavefronts the launch rule gives the contig: its rows, the slots, or what fits 1 GiB of scratch."""
+    M, npl, slots, _, _ = STRIDE[case]
+    nck = (int(ob[:, 0].max()) + 63) // 64 - 1
+    per_wave = 64 * 3 * 64 * npl * 4 + nck * 64 * npl * 8
+    return min(len(ob), slots, (1 << 30) // per_wave), per_wave
+
+
+def stride_rows(case, im, contigs, c):
+    """stay / up / down of contig c, the launch printed; contig 0: fewer wavefronts than rows, asserted."""
+    v = trans(im, c)
+    waves, L = im.describe()["transition_waves"], len(contigs[c])
+    want, per_wave = stride_waves(case, contigs[c])
+    print(f"{case} contig {c}: {L} rows on {waves} wavefronts ({per_wave} bytes of scratch each)")
+    assert waves == want, (case, c, waves, want)
+    if c == 0:
+        assert waves < L, (case, waves, L)
+    return v
+
+
+@pytest.mark.parametrize("case", sorted(STRIDE))
+def test_second_row_of_a_wavefront(engine_opt, case):
+    """More rows than wavefronts - by the 1 GiB scratch cap at one state per lane (rows of many blocks: wavefronts that parked
+    checkpoints go on to another row), by the 4096 / 1024 slots at 2, 8 and 16 states per lane: every column against the oracle,
+    the sums over the rows against the engine's xisum, the windows of 100 base pairs."""
+    im, contigs = stride_manager(case, engine_opt)
+    if case == "stride:M64":
+        spans = contigs[0][:, 0]
+        assert int((spans > 64).sum()) == 543 and int(spans.max()) == 100_000
+        assert stride_waves(case, contigs[0]) == (1264, 848_896)
+    refs = oracle(case, im, contigs)
+    xis = im.xisums
+    worst = {"scale": 0.0, "large": 0.0, "sum": 0.0, "stat": 0.0}
+    for c, ob in enumerate(contigs):
+        label = f"{case} contig {c}"
+        spans = ob[:, 0]
+        v = stride_rows(case, im, contigs, c)
+        w = check_rows(v, refs[c], spans, label)
+        w["stat"] = check_statistic(v, xis[c], label)
+        for k in worst:
+            worst[k] = max(worst[k], w[k])
+        W, total = 100, int(spans.sum())
+        got = im.posterior_transition_windows(c, W)
+        assert im.describe()["transition_waves"] == stride_waves(case, ob)[0]
+        want, covered = transref.transition_windows(v, spans, W)
+        assert got.dtype == np.float64 and got.shape == want.shape == (3, -(-total // W)), (label, got.shape)
+        tol = (W + 8) * EPS
+        err = np.abs(got - want)
+        assert not (err > tol * np.abs(want)).any(), f"{label}: windows off, worst {np.max(err / np.maximum(want, 1e-300)) / EPS:.1f} eps"
+        serr = np.abs(got.sum(axis=0) - covered) / covered
+        assert np.all(serr <= tol), f"{label}: a window's three rows miss its base pairs by {serr.max() / EPS:.1f} eps (bar {W + 8})"
+    print(f"{case}: WORST scale {worst['scale']:.2e} large {worst['large']:.2e} sum {worst['sum']:.2e} stat {worst['stat']:.2e}")
+
+
+@pytest.mark.parametrize("case", ["stride:M64", "stride:M300", "stride:M520"])
+def test_second_row_gives_the_same_bits(engine_opt, case):
+    """Repetition, the other posterior products in between, poisoned allocations: the same bits - a second row that reads what the
+    first left in the wavefront's scratch shows here."""
+    engine_opt("SMCPP_DEBUG_POISON", None)
+    im, contigs = stride_manager(case, engine_opt)
+    nc = len(contigs)
+
+    def all_products(im):
+        out = []
+        for c in range(nc):
+            out.append({"rows": stride_rows(case, im, contigs, c), "w100": im.posterior_transition_windows(c, 100)})
+        return out
+
+    first = all_products(im)
+    for a, b in zip(all_products(im), first):
+        same_bits(a, b)
+    for c in reversed(range(nc)):
+        im.posterior_windows(c, 100)
+        im.posterior_summary(nc - 1 - c)
+        im.posterior_sample_rows(c, 2, 5)
+        im.posterior_columns(0, normalize=False)
+        assert np.array_equal(im.posterior_transition_windows(c, 100), first[c]["w100"])
+        assert np.array_equal(trans(im, c), first[c]["rows"])
+    del im
+    engine_opt("SMCPP_DEBUG_POISON", "255")
+    im, contigs = stride_manager(case, engine_opt)
+    poisoned = all_products(im)
+    del im
+    engine_opt("SMCPP_DEBUG_POISON", None)
+    for a, b in zip(first, poisoned):
         same_bits(b, a)
 
 
