@@ -408,6 +408,38 @@ int smcpp_posterior_sample_rows(smcpp_im *im, int contig, unsigned long long see
 int smcpp_posterior_sample_positions(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths,
                                      long long pos0, long long pos1, int *out /* [npaths x (pos1 - pos0)] row-major */);
 
+/* ---- posterior positions (posterior_pos_dev.hpp): the posterior of SINGLE positions of contig c, as a distribution.  Conventions
+ * as for the path sampler: caller's rows l = 1 .. L with spans s_l, P_l = s_1 + .. + s_l, positions 0 .. N with N = P_L; position 0
+ * is column 0, row l covers positions P_{l-1} + 1 .. P_l;
+ *     a_0 = pi, a_p = e_p o (T^T a_{p-1});   b_N = 1, b_{p-1} = T (e_p o b_p);   gamma_p(i) = a_p(i) b_p(i) / sum_m a_p(m) b_p(m).
+ * gamma_0 is column 0 of smcpp_posterior_columns(normalize = 1), and the marginal of the one position of a row with s_l = 1 is that
+ * row's column of it, bit for bit.  Inside longer rows the device walks from what the E-step stored - the float alpha at the row's
+ * start (its entries at the 1e-10 floor restored from the row before where that row is one position), beta at its end, the O(M)
+ * scan steps in between, a_p kept as floats - so gamma_p agrees with the float64 one to the accuracy
+ * of the per-row posterior (bar 2e-5; tests/test_gpu_posterior_positions.py holds every position to it).  A grid is
+ * range(pos0, pos1, step) over 0 .. N, npos = ceil((pos1 - pos0) / step) positions.  A value is a pure function of the stored vectors
+ * and the position: not of the grid, the launch shape, the call order or what ran before.
+ * Preconditions are those of smcpp_posterior_transitions, and: 0 <= pos0 < pos1 <= N + 1, step >= 1, window_bp >= 1, 0 <= nq <= 8,
+ * levels in (0, 1), finite weights, at most 2^31 - 1 output elements per array, at most 1 GiB of scratch (the checkpoints of the
+ * longest walked row; the segment sums of the exact windows).  Every failure happens before anything is launched.
+ *
+ * smcpp_posterior_positions: gamma_p of every grid position. */
+int smcpp_posterior_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step,
+                              double *out /* [M x npos] row-major */);
+/* smcpp_posterior_position_summary: per grid position, without storing the column: argmax = the lowest state that attains the
+ * maximum; mean = sum_m weights[m] gamma_p(m) (skipped when weights is NULL); per level q_k of nq <= 8:
+ * qstate = min{ m : sum_{i <= m} gamma_p(i) >= q_k }, clamped to M - 1. */
+int smcpp_posterior_position_summary(smcpp_im *im, int contig, long long pos0, long long pos1, long long step,
+                                     const double *weights /* [M] or NULL */, int nq, const double *q /* [nq] */,
+                                     int *argmax /* [npos] or NULL */, double *mean /* [npos] or NULL */,
+                                     int *qstate /* [nq x npos] row-major or NULL */);
+/* smcpp_posterior_windows_exact: windows as in smcpp_posterior_windows (base pair b is position b + 1), but exact on long rows:
+ *     out[:, w] = (1 / covered_w) sum_{p - 1 in [w W, min((w + 1) W, N))} gamma_p.
+ * A row inside one window contributes s_l p[:, l] from the stored per-row posterior; a row that k >= 1 window boundaries cut is walked
+ * and contributes its k + 1 segment sums.  The terms of a window are added in ascending position order. */
+int smcpp_posterior_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
+                                  double *out /* [M x n_windows] row-major; NULL: only n_windows */);
+
 #ifdef __cplusplus
 }
 #endif

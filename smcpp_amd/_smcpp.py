@@ -264,6 +264,52 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_posterior_sample_positions(*args, E.iptr(out)))
         return out
 
+    def _grid(self, c, pos0, pos1, step):
+        c = int(c)
+        if pos1 is None:
+            pos1 = int(self._observations[c][:, 0].sum(dtype=np.int64)) + 1 if 0 <= c < self._num_hmms else 1     # (a bad contig index: the engine raises)
+        pos0, pos1, step = int(pos0), int(pos1), int(step)
+        npos = max(0, -(-(pos1 - pos0) // step)) if step >= 1 else 0          # (bad arguments: the engine raises before npos is used)
+        return c, pos0, pos1, step, npos
+
+    def posterior_positions(self, c=0, pos0=0, pos1=None, step=1):
+        """`[M, npos]`: the posterior of the single positions `range(pos0, pos1, step)` of `0 .. P_L` of contig `c` (position 0 is
+        column 0, row `l` covers positions `P_{l-1} + 1 .. P_l`; default: all of them), every column summing to one.
+        (include/smcpp_engine.h: smcpp_posterior_positions.)"""
+        c, pos0, pos1, step, npos = self._grid(c, pos0, pos1, step)
+        E.check(E.lib().smcpp_posterior_positions(self._im, c, pos0, pos1, step, None))            # (the checks alone)
+        out = np.empty((self.M, npos))
+        E.check(E.lib().smcpp_posterior_positions(self._im, c, pos0, pos1, step, E.dptr(out)))
+        return out
+
+    def posterior_position_summary(self, c=0, weights=None, quantiles=(), pos0=0, pos1=None, step=1):
+        """Per position of the grid `range(pos0, pos1, step)` of contig `c`, without fetching the columns: dict of `argmax` (the
+        lowest state of maximal posterior), `mean` (`sum_m weights[m] gamma_p(m)`; absent without weights) and `qstate`
+        `[len(quantiles), npos]`, the first state at which the cumulative posterior reaches each level (at most 8, each in (0, 1))."""
+        c, pos0, pos1, step, npos = self._grid(c, pos0, pos1, step)
+        q = aca(np.atleast_1d(np.asarray(quantiles, dtype=np.float64)).reshape(-1))
+        w = None if weights is None else aca(weights, dtype=np.float64).reshape(-1)
+        if w is not None and len(w) != self.M:
+            raise RuntimeError(f"posterior_position_summary: {len(w)} weights for {self.M} hidden states")
+        args = (self._im, c, pos0, pos1, step, E.dptr(w), len(q), E.dptr(q) if len(q) else None)
+        E.check(E.lib().smcpp_posterior_position_summary(*args, None, None, None))                 # (the checks alone)
+        ret = {"argmax": np.empty(npos, dtype=np.int32), "qstate": np.empty((len(q), npos), dtype=np.int32)}
+        if w is not None:
+            ret["mean"] = np.empty(npos)
+        E.check(E.lib().smcpp_posterior_position_summary(*args, E.iptr(ret["argmax"]), E.dptr(ret.get("mean")),
+                                                         E.iptr(ret["qstate"]) if len(q) else None))
+        return ret
+
+    def posterior_windows_exact(self, c=0, window=10_000):
+        """`[M, ceil(P_L / window)]`: the posterior of contig `c` averaged over windows of `window` base pairs like
+        `posterior_windows`, but exact on rows that a window boundary cuts: their interior is walked position by position
+        instead of being apportioned uniformly."""
+        nw = C.c_longlong(0)
+        E.check(E.lib().smcpp_posterior_windows_exact(self._im, int(c), int(window), C.byref(nw), None))
+        out = np.empty((self.M, nw.value))
+        E.check(E.lib().smcpp_posterior_windows_exact(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
+        return out
+
     @property
     def xisums(self):
         ret = []

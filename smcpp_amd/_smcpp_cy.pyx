@@ -113,6 +113,9 @@ cdef extern from "smcpp_engine.h":
     int smcpp_posterior_transition_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
     int smcpp_posterior_sample_rows(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths, long long start, long long stop, long long step, int *state, int *up, int *down) nogil
     int smcpp_posterior_sample_positions(smcpp_im *im, int contig, unsigned long long seed, long long path0, long long npaths, long long pos0, long long pos1, int *out) nogil
+    int smcpp_posterior_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, double *out) nogil
+    int smcpp_posterior_position_summary(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, const double *weights, int nq, const double *q, int *argmax, double *mean, int *qstate) nogil
+    int smcpp_posterior_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
 # --- end generated ---
 
 aca = np.ascontiguousarray
@@ -488,6 +491,73 @@ cdef class _PyInferenceManager:
             rc = smcpp_posterior_sample_positions(self._im, cc, sd, k0, nk, a, b, op)
         _check(rc)
         return out[:n * w].reshape(n, w).copy()
+
+    def _grid(self, c, pos0, pos1, step):
+        c = int(c)
+        if pos1 is None:
+            pos1 = int(self._keep[c][:, 0].sum(dtype=np.int64)) + 1 if 0 <= c < self._num_hmms else 1
+        pos0, pos1, step = int(pos0), int(pos1), int(step)
+        npos = max(0, -(-(pos1 - pos0) // step)) if step >= 1 else 0
+        return pos0, pos1, step, npos
+
+    def posterior_positions(self, c=0, pos0=0, pos1=None, step=1):
+        pos0, pos1, step, npos = self._grid(c, pos0, pos1, step)
+        cdef int M = len(self._hs) - 1, cc = c, rc
+        cdef long long a = pos0, b = pos1, st = step
+        with nogil:
+            rc = smcpp_posterior_positions(self._im, cc, a, b, st, NULL)                             # (the checks alone)
+        _check(rc)
+        cdef np.ndarray[double, ndim=2] out = np.empty((M, max(npos, 1)))
+        cdef double *op = &out[0, 0]
+        with nogil:
+            rc = smcpp_posterior_positions(self._im, cc, a, b, st, op)
+        _check(rc)
+        return out
+
+    def posterior_position_summary(self, c=0, weights=None, quantiles=(), pos0=0, pos1=None, step=1):
+        pos0, pos1, step, npos = self._grid(c, pos0, pos1, step)
+        cdef int M = len(self._hs) - 1, cc = c, rc, nq
+        cdef long long a = pos0, b = pos1, st = step
+        cdef np.ndarray[double, ndim=1] q = aca(np.atleast_1d(np.asarray(quantiles, dtype=np.float64)).reshape(-1))
+        cdef np.ndarray[double, ndim=1] w = np.zeros(1) if weights is None else aca(weights, dtype=np.float64).reshape(-1)
+        if weights is not None and len(w) != M:
+            raise RuntimeError("posterior_position_summary: %d weights for %d hidden states" % (len(w), M))
+        nq = len(q)
+        cdef np.ndarray[double, ndim=1] mean = np.empty(max(npos, 1))
+        cdef np.ndarray[int, ndim=1] argmax = np.empty(max(npos, 1), dtype=np.int32)
+        cdef np.ndarray[int, ndim=1] qstate = np.empty(max(nq * npos, 1), dtype=np.int32)
+        cdef double *wp = NULL
+        cdef double *qp = NULL
+        cdef double *mp = NULL
+        cdef int *qsp = NULL
+        cdef int *amp = &argmax[0]
+        if weights is not None:
+            wp = &w[0]
+            mp = &mean[0]
+        if nq:
+            qp = &q[0]
+            qsp = &qstate[0]
+        with nogil:
+            rc = smcpp_posterior_position_summary(self._im, cc, a, b, st, wp, nq, qp, NULL, NULL, NULL)   # (the checks alone)
+        _check(rc)
+        with nogil:
+            rc = smcpp_posterior_position_summary(self._im, cc, a, b, st, wp, nq, qp, amp, mp, qsp)
+        _check(rc)
+        ret = {"argmax": argmax[:npos], "qstate": qstate[:nq * npos].reshape(nq, npos)}
+        if weights is not None:
+            ret["mean"] = mean[:npos]
+        return ret
+
+    def posterior_windows_exact(self, c=0, window=10_000):
+        cdef int M = len(self._hs) - 1, cc = c, rc
+        cdef long long W = window, nw = 0
+        _check(smcpp_posterior_windows_exact(self._im, cc, W, &nw, NULL))
+        cdef np.ndarray[double, ndim=2] out = np.empty((M, max(nw, 1)))
+        cdef double *op = &out[0, 0]
+        with nogil:
+            rc = smcpp_posterior_windows_exact(self._im, cc, W, &nw, op)
+        _check(rc)
+        return out[:, :nw] if nw < out.shape[1] else out
 
     property xisums:
         def __get__(self):

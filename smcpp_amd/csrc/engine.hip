@@ -41,6 +41,7 @@
 #include "posterior_dev.hpp"    // products of the per-row posteriors: columns, per-column summaries, windows
 #include "posterior_trans_dev.hpp"   // posterior transition products: stay / up / down per row and per window
 #include "posterior_paths_dev.hpp"   // posterior paths: forward filtering, backward sampling (state / up / down per row, per position)
+#include "posterior_pos_dev.hpp"     // posterior positions: the marginal of single positions on a grid, its summaries, exact windows
 
 // The engine is one translation unit in seven parts (each part sees everything above it):
 #include "engine_base.hpp"        // logging, pinned arena, device buffers, the device route of the cold preparation (DevPrep, TwoPopDevCsfs)

@@ -706,6 +706,253 @@ int smcpp_posterior_sample_positions(smcpp_im *im, int c, unsigned long long see
     API_END
 }
 
+// ---- posterior positions (posterior_pos_dev.hpp) ----
+// Positions 0 .. N of contig c; engine row i covers positions q0 + 1 .. q0 + span.  The item table of a grid: the engine rows that
+// hold a grid position, ascending - a caller's row of ONE position (and position 0) as a stored item, every other one to walk.
+void smcpp_im::post_positions_grid(int c, long long pos0, long long pos1, long long step) {
+    const int Le = Ls[c];
+    const std::vector<long long> &P = user_prefix[c];
+    pq_items.clear();
+    pq_start.clear();
+    pq_walked = 0; pq_smax = 1; pq_nseg = 0;
+    if (pos0 == 0) pq_items.push_back(PqItem{0, 0, 0, 0, 0});
+    long long q0 = 0;
+    for (int i = 1; i <= Le; ++i) {
+        const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+        const int span = ri.gid >= 0 ? groups[ri.gid].span : 1;
+        const long long end = q0 + span, lo = std::max(q0 + 1, pos0);
+        if (q0 + 1 >= pos1) break;
+        if (end >= pos0) {
+            const long long g = pos0 + (lo - pos0 + step - 1) / step * step;       // the first grid position of the row, if any
+            if (g <= end && g < pos1) {
+                const int l = split_spans ? piece_row[c][i] : i;
+                if (P[l] - P[l - 1] == 1) pq_items.push_back(PqItem{end, i, l, 0, 0});
+                else {
+                    pq_items.push_back(PqItem{end, i, -1, 0, 0});
+                    ++pq_walked;
+                    pq_smax = std::max(pq_smax, span);
+                }
+            }
+        }
+        q0 = end;
+    }
+}
+
+// The item table of the exact windows: the engine rows of every caller's row that a window boundary cuts, each with the index of its
+// first segment (a row that reaches into k + 1 windows has k + 1 segments).
+void smcpp_im::post_positions_segments(int c, long long W) {
+    const int Le = Ls[c];
+    const std::vector<long long> &P = user_prefix[c];
+    pq_items.clear();
+    pq_start.clear();
+    pq_walked = 0; pq_smax = 1; pq_nseg = 0;
+    long long q0 = 0;
+    for (int i = 1; i <= Le; ++i) {
+        const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+        const int span = ri.gid >= 0 ? groups[ri.gid].span : 1;
+        const long long end = q0 + span;
+        const int l = split_spans ? piece_row[c][i] : i;
+        if (P[l - 1] / W != (P[l] - 1) / W) {
+            if (pq_nseg > (1LL << 31) - 1 - ((end - 1) / W - q0 / W + 1))
+                throw std::runtime_error("posterior positions: more than 2^31 - 1 segments of cut rows (widen the window)");
+            pq_items.push_back(PqItem{end, i, -1, (int)pq_nseg, 0});
+            pq_start.push_back(q0);
+            pq_nseg += (end - 1) / W - q0 / W + 1;
+            ++pq_walked;
+            pq_smax = std::max(pq_smax, span);
+        }
+        q0 = end;
+    }
+}
+
+void smcpp_im::post_positions_scratch_check(size_t extra_bytes) {
+    const size_t MS = (size_t)64 * NPL;
+    const size_t per_wave = (size_t)PQ_BLK * MS * sizeof(float) + (size_t)((pq_smax + PQ_BLK - 1) / PQ_BLK - 1) * MS * sizeof(double);
+    if (per_wave > (1ull << 30))
+        throw std::runtime_error("posterior positions: the checkpoints of a row of " + std::to_string(pq_smax) + " positions exceed the "
+                                 "scratch cap of 1 GiB");
+    if (extra_bytes > (1ull << 30))
+        throw std::runtime_error("posterior positions: the segment sums of the cut rows (" + std::to_string(pq_nseg) + " vectors) exceed "
+                                 "the scratch cap of 1 GiB (widen the window)");
+}
+
+// the column sums of every caller's row, by the kernel that serves smcpp_posterior_summary: p is the same number in every product
+const double *smcpp_im::post_colsum(int c, const PostSource &src) {
+    PostSel all;
+    all.start = 0; all.step = 1; all.ncols = (long long)user_Ls[c] + 1;
+    PostLevels none;
+    none.nq = 0;
+    for (int k = 0; k < 8; ++k) none.q[k] = 2.0;
+    d_pq_colsum.alloc((size_t)all.ncols);
+    hipLaunchKernelGGL(k_post_summary, dim3((unsigned)ceil_div(all.ncols, PS_TL)), dim3(256), 0, stream, M, Mp, all, src.rows, src.g0,
+                       (const double *)nullptr, none, d_pq_colsum.p, (int *)nullptr, (double *)nullptr, (int *)nullptr);
+    HIPCHK(hipGetLastError());
+    return d_pq_colsum.p;
+}
+
+// Launches k_post_positions over pq_items (not empty) with sink `kind`; the sink's fields of pa are the caller's, the rest is set here.
+// The arguments have been checked.
+void smcpp_im::post_positions_launch(int c, int kind, PqArgs &pa) {
+    const int MS = 64 * NPL;
+    d_pt_gen.upload(ss_gen, stream);                   // (ss_gen is a member: it outlives the copy)
+    SsArgs sa = SsArgs();
+    sa.M = M; sa.Mp = Mp;
+    const double *gd = d_pt_gen.p;
+    sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
+    sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
+    sa.c0 = ss_c0;
+    pa.M = M; pa.Mp = Mp; pa.base = contig_base[c];
+    pa.nck = (pq_smax + PQ_BLK - 1) / PQ_BLK - 1;
+    pa.nitems = (int)pq_items.size();
+    // one wavefront per item, persistent; fewer of them where the scratch of a wavefront is large: at most 1 GiB in all
+    const size_t per_wave = (size_t)PQ_BLK * MS * sizeof(float) + (size_t)pa.nck * MS * sizeof(double);
+    const long long want = std::min<long long>(pa.nitems, NPL >= 8 ? 1024 : 4096);
+    const int nw = (int)std::max<long long>(1, std::min<long long>(want, (long long)((1ull << 30) / per_wave)));
+    d_pq_items.upload(pq_items, stream);               // (a member: it outlives the copy)
+    d_pq_park.alloc((size_t)nw * PQ_BLK * MS);
+    d_pq_ckpt.alloc(std::max<size_t>(1, (size_t)nw * pa.nck * MS));
+    pa.rowinfo = d_rowinfo.p; pa.g_span = d_g_span.p; pa.E = d_E.p; pa.alpha = d_alpha.p; pa.beta = d_beta.p;
+    pa.items = d_pq_items.p; pa.park = d_pq_park.p; pa.ckpt = d_pq_ckpt.p;
+    pq_waves = nw;
+    const dim3 grid(ceil_div(nw, 4)), block(256);
+#define PQ_(x, S) case x: hipLaunchKernelGGL((k_post_positions<x, S>), grid, block, 0, stream, sa, pa, nw); break;
+#define PQ_ALL(S) switch (NPL) { PQ_(1, S) PQ_(2, S) PQ_(3, S) PQ_(4, S) PQ_(8, S) default: PQ_(16, S) }
+    if (kind == 0) PQ_ALL(PqColumns)
+    else if (kind == 1) PQ_ALL(PqSummary)
+    else PQ_ALL(PqSegments)
+#undef PQ_ALL
+#undef PQ_
+    HIPCHK(hipGetLastError());
+}
+
+// pos0 / pos1 / step of a grid over the positions 0 .. N of contig c -> the number of grid positions
+static long long post_positions_check_grid(smcpp_im *im, int c, long long pos0, long long pos1, long long step) {
+    const long long N = im->user_prefix[c][im->user_Ls[c]];
+    if (pos0 < 0) throw std::runtime_error("posterior positions: pos0 < 0");
+    if (pos1 > N + 1) throw std::runtime_error("posterior positions: pos1 > P_L + 1 (the contig has " + std::to_string(N + 1) + " positions)");
+    if (pos0 >= pos1) throw std::runtime_error("posterior positions: empty grid (pos0 >= pos1)");
+    if (step < 1) throw std::runtime_error("posterior positions: step < 1");
+    return (pos1 - pos0 + step - 1) / step;
+}
+static void post_positions_cap(long long per_pos, long long npos, const char *what) {
+    if (npos > ((1LL << 31) - 1) / std::max<long long>(1, per_pos))
+        throw std::runtime_error(std::string("posterior positions: ") + what + " (" + std::to_string(per_pos) + " x " +
+                                 std::to_string(npos) + " positions) exceed the cap of 2^31 - 1 elements per array: ask for a "
+                                 "narrower or a coarser grid");
+}
+
+int smcpp_posterior_positions(smcpp_im *im, int c, long long pos0, long long pos1, long long step, double *out) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    im->post_transitions_check();
+    const long long npos = post_positions_check_grid(im, c, pos0, pos1, step);
+    post_positions_cap(im->M, npos, "the columns");
+    im->post_positions_grid(c, pos0, pos1, step);
+    im->post_positions_scratch_check(0);
+    if (!out) return 0;
+    const smcpp_im::PostSource src = im->post_source(c);
+    PqArgs pa = PqArgs();
+    pa.rows = src.rows; pa.g0 = src.g0; pa.colsum = im->post_colsum(c, src);
+    pa.pos0 = pos0; pa.pos1 = pos1; pa.step = step; pa.npos = npos;
+    const size_t cells = (size_t)im->M * npos;
+    im->d_post_out.alloc(cells);
+    pa.out = im->d_post_out.p;
+    im->post_positions_launch(c, 0, pa);
+    HIPCHK(hipMemcpyAsync(out, im->d_post_out.p, sizeof(double) * cells, hipMemcpyDeviceToHost, im->stream));
+    HIPCHK(hipStreamSynchronize(im->stream));
+    API_END
+}
+
+int smcpp_posterior_position_summary(smcpp_im *im, int c, long long pos0, long long pos1, long long step, const double *weights, int nq,
+                                     const double *q, int *argmax, double *mean, int *qstate) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    im->post_transitions_check();
+    const long long npos = post_positions_check_grid(im, c, pos0, pos1, step);
+    if (nq < 0 || nq > 8) throw std::runtime_error("posterior position summary: between 0 and 8 quantile levels");
+    if (nq > 0 && !q) throw std::runtime_error("posterior position summary: quantile levels are missing");
+    PqArgs pa = PqArgs();
+    pa.lv.nq = nq;
+    for (int k = 0; k < 8; ++k) pa.lv.q[k] = 2.0;
+    for (int k = 0; k < nq; ++k) {
+        if (!(q[k] > 0.0 && q[k] < 1.0)) throw std::runtime_error("posterior position summary: a quantile level must lie in (0, 1)");
+        pa.lv.q[k] = q[k];
+    }
+    const int M = im->M;
+    if (weights)
+        for (int i = 0; i < M; ++i)
+            if (!std::isfinite(weights[i])) throw std::runtime_error("posterior position summary: weight " + std::to_string(i) + " is not finite");
+    post_positions_cap(std::max(1, nq), npos, "the summaries");
+    im->post_positions_grid(c, pos0, pos1, step);
+    im->post_positions_scratch_check(0);
+    const bool want_mean = weights && mean, want_q = nq > 0 && qstate;
+    if (!argmax && !want_mean && !want_q) return 0;
+    const smcpp_im::PostSource src = im->post_source(c);
+    hipStream_t s = im->stream;
+    pa.rows = src.rows; pa.g0 = src.g0; pa.colsum = im->post_colsum(c, src);
+    pa.pos0 = pos0; pa.pos1 = pos1; pa.step = step; pa.npos = npos;
+    if (argmax) { im->d_post_arg.alloc((size_t)npos); pa.argmax = im->d_post_arg.p; }
+    if (want_mean) {
+        im->d_post_mean.alloc((size_t)npos);
+        im->d_post_w.alloc((size_t)M);
+        HIPCHK(hipMemcpyAsync(im->d_post_w.p, weights, sizeof(double) * M, hipMemcpyHostToDevice, s));
+        pa.w = im->d_post_w.p; pa.mean = im->d_post_mean.p;
+    }
+    if (want_q) { im->d_post_q.alloc((size_t)nq * npos); pa.qstate = im->d_post_q.p; }
+    else pa.lv.nq = 0;
+    im->post_positions_launch(c, 1, pa);
+    if (argmax) HIPCHK(hipMemcpyAsync(argmax, im->d_post_arg.p, sizeof(int) * npos, hipMemcpyDeviceToHost, s));
+    if (want_mean) HIPCHK(hipMemcpyAsync(mean, im->d_post_mean.p, sizeof(double) * npos, hipMemcpyDeviceToHost, s));
+    if (want_q) HIPCHK(hipMemcpyAsync(qstate, im->d_post_q.p, sizeof(int) * (size_t)nq * npos, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
+int smcpp_posterior_windows_exact(smcpp_im *im, int c, long long window_bp, long long *n_windows, double *out) {
+    API_BEGIN
+    post_need_gamma(im, c);
+    if (window_bp < 1) throw std::runtime_error("posterior windows: window_bp < 1");
+    im->post_transitions_check();
+    const std::vector<long long> &P = im->user_prefix[c];
+    const long long L = im->user_Ls[c];
+    const long long nwin = (P[L] + window_bp - 1) / window_bp;
+    if (n_windows) *n_windows = nwin;
+    if (!out) return 0;
+    post_positions_cap(im->M, nwin, "the windows");
+    im->post_positions_segments(c, window_bp);
+    const int M = im->M, Mp = im->Mp, MS = 64 * im->NPL;
+    im->post_positions_scratch_check((size_t)im->pq_nseg * MS * sizeof(double));
+    const smcpp_im::PostSource src = im->post_source(c);
+    hipStream_t s = im->stream;
+    if (im->d_user_prefix.size() != (size_t)im->n_contigs) im->d_user_prefix.resize(im->n_contigs);
+    if (!im->d_user_prefix[c].p) {
+        im->d_user_prefix[c].upload(P, s);             // (P is a member: it outlives the copy)
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const double *colsum = im->post_colsum(c, src);
+    const int nit = (int)im->pq_items.size();
+    im->d_pq_seg.alloc(std::max<size_t>(1, (size_t)im->pq_nseg * MS));
+    im->d_pq_start.upload(im->pq_start, s);            // (a member: it outlives the copy)
+    if (nit > 0) {
+        PqArgs pa = PqArgs();
+        pa.W = window_bp; pa.seg = im->d_pq_seg.p;
+        pa.step = 1;
+        im->post_positions_launch(c, 2, pa);
+    } else {
+        im->pq_waves = 0;
+        im->d_pq_items.alloc(1);
+        im->d_pq_start.alloc(1);
+    }
+    im->d_post_out.alloc((size_t)M * nwin);
+    hipLaunchKernelGGL(k_post_windows_exact, dim3((unsigned)ceil_div(nwin, 4), (unsigned)ceil_div(M, 64)), dim3(256), 0, s, M, Mp, MS, L,
+                       window_bp, nwin, (const long long *)im->d_user_prefix[c].p, src.rows, colsum, (const PqItem *)im->d_pq_items.p,
+                       (const long long *)im->d_pq_start.p, nit, (const double *)im->d_pq_seg.p, im->d_post_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, im->d_post_out.p, sizeof(double) * (size_t)M * nwin, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
 int smcpp_gamma_cols(smcpp_im *im, int c) {
     if (c < 0 || c >= im->n_contigs) return -1;
     return im->gamma_valid ? im->user_Ls[c] + 1 : 1;

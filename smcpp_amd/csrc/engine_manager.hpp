@@ -226,6 +226,24 @@ struct smcpp_im {
     // rows: [3][npaths][ncols] of the selection (ncols > 0), pos: [npaths][pos1 - pos0] (pos1 > pos0), on the device, on `stream`
     PostPaths post_paths(int c, unsigned long long seed, long long path0, long long npaths, long long start, long long step,
                          long long ncols, long long pos0, long long pos1);
+    // posterior positions (posterior_pos_dev.hpp, smcpp_posterior_positions / _position_summary / _windows_exact): the item table of
+    // the last call (engine rows to walk, positions whose marginal is stored), the wavefronts' scratch, the segment sums of the
+    // rows a window boundary cuts
+    std::vector<PqItem> pq_items;
+    std::vector<long long> pq_start;              // segments: the position in front of every item
+    DevBuf<PqItem> d_pq_items;
+    DevBuf<long long> d_pq_start;
+    DevBuf<float> d_pq_park;
+    DevBuf<double> d_pq_ckpt, d_pq_seg, d_pq_colsum;
+    int pq_waves = 0;                             // wavefronts of the last position call (smcpp_describe)
+    long long pq_walked = 0;                      // engine rows it walked
+    int pq_smax = 1;                              // the longest of them
+    long long pq_nseg = 0;
+    void post_positions_grid(int c, long long pos0, long long pos1, long long step);     // -> pq_items (host)
+    void post_positions_segments(int c, long long W);                                    // -> pq_items, pq_start, pq_nseg (host)
+    void post_positions_scratch_check(size_t extra_bytes);                               // throws beyond the 1 GiB cap
+    const double *post_colsum(int c, const PostSource &src);                             // [Lu + 1] column sums on the device
+    void post_positions_launch(int c, int kind, PqArgs &pa);
     // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;

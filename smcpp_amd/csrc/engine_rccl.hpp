@@ -257,6 +257,8 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // last posterior transition call (0: none yet); a wavefront takes more than one batch / row where there are fewer of them
         s += ", \"path_batch\": " + std::to_string(im->pp_batch) + ", \"path_batches\": " + std::to_string(im->pp_batches);
         s += ", \"path_waves\": " + std::to_string(im->pp_waves) + ", \"transition_waves\": " + std::to_string(im->pt_waves);
+        // ... and of the last posterior position call: its wavefronts and the engine rows it walked
+        s += ", \"position_waves\": " + std::to_string(im->pq_waves) + ", \"position_rows_walked\": " + std::to_string(im->pq_walked);
     }
     s += "}";
     if (buf && cap > 0) {

@@ -104,7 +104,7 @@ def average_coal_times(model, hidden_states):
 
 def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
                        start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False, transitions=False,
-                       paths=0, seed=0):
+                       paths=0, seed=0, grid=None, exact_windows=False):
     """What a posterior decoding is reduced to, computed on the device without ever fetching the `[M, L+1]` matrix (arguments and
     set-up as `posterior`: hidden states, the prepended missing row, `start` / `end` / `thinning`, one or two populations).
     Returns `(hidden_states, products)`; `products[c]` is a dict for contig c:
@@ -128,6 +128,12 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
       `path_state`  `[K, L+1]` int32: the state of sampled path k at the row's last position (column 0: at position 0);
       `path_up`, `path_down`  `[K, L+1]` int32: the number of the row's positions at which path k moves to a higher (older) / lower
                     state; `(path_up + path_down).sum(axis=1)` is the number of breakpoints of path k.
+    With `grid=step` (positions `0 .. P`: position 0 is column 0, row l covers positions `P_{l-1} + 1 .. P_l`) each dict gains the
+    posterior of single positions, summarised on the grid `range(0, P + 1, step)` (`im.posterior_position_summary`):
+      `grid_positions`   `[npos]` int64, the positions;
+      `grid_path`, `grid_mean_tmrca`, `grid_qstate`   as `path`, `mean_tmrca`, `qstate`, per grid position instead of per column.
+    With `exact_windows=True` (and `window=W`) `windows` comes from `im.posterior_windows_exact`: rows that a window boundary cuts
+    are walked position by position instead of being apportioned uniformly.
     `return_manager=True` appends the inference manager."""
     hs, obs, im = _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end,
                                 thinning)
@@ -138,7 +144,7 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
         sm = im.posterior_summary(c, weights=w, quantiles=quantiles)
         prod = {"sites": obs[c][:, 0].copy(), "path": sm["argmax"], "mean_tmrca": sm["mean"], "qstate": sm["qstate"]}
         if window is not None:
-            prod["windows"] = im.posterior_windows(c, window)
+            prod["windows"] = im.posterior_windows_exact(c, window) if exact_windows else im.posterior_windows(c, window)
         if transitions:
             tr = im.posterior_transitions(c)
             prod["transitions"] = np.stack([tr["stay"], tr["up"], tr["down"]])
@@ -147,6 +153,11 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
         if paths > 0:
             pr = im.posterior_sample_rows(c, n_paths=paths, seed=seed)
             prod["path_state"], prod["path_up"], prod["path_down"] = pr["state"], pr["up"], pr["down"]
+        if grid is not None:
+            total = int(obs[c][:, 0].sum(dtype=np.int64))
+            gs = im.posterior_position_summary(c, weights=w, quantiles=quantiles, pos0=0, pos1=total + 1, step=int(grid))
+            prod["grid_positions"] = np.arange(0, total + 1, int(grid), dtype=np.int64)
+            prod["grid_path"], prod["grid_mean_tmrca"], prod["grid_qstate"] = gs["argmax"], gs["mean"], gs["qstate"]
         products.append(prod)
     if return_manager:
         return hs, products, im
@@ -165,11 +176,12 @@ def save_npz(path, hs, gammas, sites, names):
 def save_products_npz(path, hs, products, names):
     """`.npz` of `posterior_products`: `hidden_states` and per file `<file>_sites`, `<file>_path`, `<file>_mean_tmrca`,
     `<file>_qstate` and, where they were asked for, `<file>_windows`, `<file>_transitions`, `<file>_transition_windows`,
-    `<file>_path_state`, `<file>_path_up`, `<file>_path_down`."""
+    `<file>_path_state`, `<file>_path_up`, `<file>_path_down`, `<file>_grid_positions`, `<file>_grid_path`, `<file>_grid_mean_tmrca`,
+    `<file>_grid_qstate`."""
     out = {"hidden_states": hs}
     for nm, prod in zip(names, products):
         for key in ("sites", "path", "mean_tmrca", "qstate", "windows", "transitions", "transition_windows", "path_state", "path_up",
-                    "path_down"):
+                    "path_down", "grid_positions", "grid_path", "grid_mean_tmrca", "grid_qstate"):
             if key in prod:
                 out[f"{nm}_{key}"] = prod[key]
     np.savez_compressed(path, **out)
