@@ -324,12 +324,19 @@ static long long shape_compress(const int *src, long long L, int ncol, DevBuf<in
                            (const long long *)A.ocum.p, dst.p);
     return nout;
 }
+// every argument check of smcpp_dev_shape, BEFORE the work area is touched: a refused call leaves the previous result, its row count
+// and its column count as they were, so a later smcpp_dev_shape_fetch still copies rows_out x ncol ints of THAT result
+static void shape_validate(int mode, long long L, int ncol, const int *rows, long long p0, long long p1, const long long *na) {
+    if (mode < 0 || mode > 3) throw std::runtime_error("smcpp_dev_shape: unknown mode");
+    if (L <= 0 || ncol < 4 || (ncol - 1) % 3 || !rows) throw std::runtime_error("data shaping: rows must be [L][1 + 3 P] int32 with L > 0");
+    if ((mode == 0 || mode == 3) && p0 <= 0) throw std::runtime_error("thinning must be positive");
+    if ((mode == 1 && p0 <= 0) || (mode == 3 && p1 <= 0)) throw std::runtime_error("the bin width must be positive");
+    if ((mode == 1 || mode == 3) && !na) throw std::runtime_error("bin_observations needs the distinguished lineages per population");
+}
 static void shape_upload(ShapeArea &A, long long L, int ncol, const int *rows) {
-    if (L <= 0 || ncol < 4 || (ncol - 1) % 3) throw std::runtime_error("data shaping: rows must be [L][1 + 3 P] int32 with L > 0");
     A.init();
     A.in.alloc((size_t)L * ncol);
     HIPCHK(hipMemcpyAsync(A.in.p, rows, sizeof(int) * (size_t)L * ncol, hipMemcpyHostToDevice, A.s));
-    A.ncol = ncol;
 }
 }  // namespace
 
@@ -342,33 +349,32 @@ extern "C" {
 int smcpp_dev_shape(int mode, long long L, int ncol, const int *rows, long long p0, long long p1, const long long *na, long long *rows_out,
                     double *kernel_ms) {
     API_BEGIN
+    shape_validate(mode, L, ncol, rows, p0, p1, na);
     ShapeArea &A = g_shape;
     shape_upload(A, L, ncol, rows);
     const int npop = (ncol - 1) / 3;
     if (mode == 1 || mode == 3) {
-        if (!na) throw std::runtime_error("bin_observations needs the distinguished lineages per population");
         std::vector<long long> h(na, na + npop);
         A.na.alloc(npop);
         HIPCHK(hipMemcpyAsync(A.na.p, h.data(), sizeof(long long) * npop, hipMemcpyHostToDevice, A.s));
         HIPCHK(hipStreamSynchronize(A.s));
     }
-    if ((mode == 0 || mode == 3) && p0 <= 0) throw std::runtime_error("thinning must be positive");
-    if ((mode == 1 && p0 <= 0) || (mode == 3 && p1 <= 0)) throw std::runtime_error("the bin width must be positive");
     HIPCHK(hipEventRecord(A.e0, A.s));
     long long n = 0;
-    if (mode == 0) { n = shape_thin(A.in.p, L, ncol, p0, p1, A.out, A); A.result = A.out.p; }
-    else if (mode == 1) { n = shape_bin(A.in.p, L, ncol, p0, A.na.p, A.out, A); A.result = A.out.p; }
-    else if (mode == 2) { n = shape_compress(A.in.p, L, ncol, A.out, A); A.result = A.out.p; }
-    else if (mode == 3) {
+    if (mode == 0) n = shape_thin(A.in.p, L, ncol, p0, p1, A.out, A);
+    else if (mode == 1) n = shape_bin(A.in.p, L, ncol, p0, A.na.p, A.out, A);
+    else if (mode == 2) n = shape_compress(A.in.p, L, ncol, A.out, A);
+    else {
         const long long n1 = shape_thin(A.in.p, L, ncol, p0, 0, A.out, A);
         const long long n2 = shape_bin(A.out.p, n1, ncol, p1, A.na.p, A.out2, A);
         n = shape_compress(A.out2.p, n2, ncol, A.out, A);
-        A.result = A.out.p;
-    } else throw std::runtime_error("smcpp_dev_shape: unknown mode");
+    }
     HIPCHK(hipEventRecord(A.e1, A.s));
     HIPCHK(hipStreamSynchronize(A.s));
     HIPCHK(hipGetLastError());
+    A.result = A.out.p;                                            // (every mode ends in `out`; set with its row and column count, once the work is done)
     A.rows_out = n;
+    A.ncol = ncol;
     if (rows_out) *rows_out = n;
     if (kernel_ms) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, A.e0, A.e1)); *kernel_ms = (double)ms; }
     API_END

@@ -6,7 +6,10 @@ pipeline as integer HIP kernels (prefix scans of the spans + binary searches + r
   * against golden G11 = the reference's own `compress_repeated_obs`;
   * against the host implementation (`smcpp_amd.data`, itself pinned by G23 / G11) on a 10^5-row un-binned contig, for every
     step and for the Thin -> Bin -> Compress pipeline, with size-independent properties at 10^6 rows (positions conserved,
-    idempotence of compress, one row per bin)."""
+    idempotence of compress, one row per bin).
+The block, tile and scan-level edges of the index code (sizes at 255 / 256 / 257 and 2047 / 2048 / 2049, the second level of the scan at
+2^21 rows, one row that holds whole emit blocks, rows without output, every thinning phase, ncol 7 and 10, more than 2^31 positions, the
+work area's reuse, refused calls) are held by tests/test_gpu_shaping_edges.py against the vectorised oracle tests/shaperef.py."""
 import os
 import zlib
 
