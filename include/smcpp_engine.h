@@ -440,6 +440,48 @@ int smcpp_posterior_position_summary(smcpp_im *im, int contig, long long pos0, l
 int smcpp_posterior_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
                                   double *out /* [M x n_windows] row-major; NULL: only n_windows */);
 
+/* ---- simulation (simulate_dev.hpp): draws of (hidden path, observations) from the model the manager holds - the process whose
+ * marginal likelihood the E-step computes.  A simulated contig has positions 1 .. N; position 0 is column 0 and carries no
+ * observation:
+ *     x_0 ~ pi;   for p = 1 .. N:   x_p ~ T(x_{p-1}, .),   o_p ~ Ebar(. | x_p).
+ * Observations are indices into an ALPHABET: alpha_keys[n_alpha], distinct key indices of the manager (rows of
+ * smcpp_get_emission_probs, the order of smcpp_get_keys), of which `quiet` (a key index that occurs in alpha_keys) is the
+ * monomorphic observation.  Ebar(k | m) = E[k][m] / sum_{k' in A} E[k'][m]: the draw always normalises over the alphabet.
+ *
+ * The walk is by EVENTS, not by positions.  With i = x_p and s_i = T(i, i) Ebar(q | i), a QUIET position keeps the state and emits q.
+ * Event e = 0, 1, .. starts at (p, i) and takes three uniforms u_0, u_1, u_2:
+ *     u_0  the quiet run  G = floor(log(1 - u_0) / log s_i)  (P(G >= g) = s_i^g), clamped to N - p; s_i = 0: G = 0; s_i >= 1:
+ *          G = N - p.  If p + G >= N the contig is finished (the event leaves no record).
+ *     u_1  the state j at the LOUD position p + G + 1, weights W_j = T(i, j) for j != i and W_i = T(i, i) (1 - Ebar(q | i)).
+ *     u_2  the key at that position, weights E[k][j] in alphabet order, the weight of q being 0 when j = i.
+ * Both draws are inverse CDFs in ASCENDING order, x = min{ j : C_j > u C_last }, clamped to the last index (the rule of the path
+ * sampler above).  x_0 is drawn in the same way from pi with the spare uniform u_3 of event 0.  u_t of event e is pp_uniform of
+ * the path sampler: Philox4x32-10 with counter = (q & 0xffffffff, q >> 32, replicate, contig), q = 4 e + t, and
+ * key = (seed & 0xffffffff, (seed >> 32) ^ 0x53494D55) - a seed shared with smcpp_posterior_sample_* does not reuse its uniforms -
+ * and u = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Contig c of the call has counter word contig0 + c, replicate r of the call
+ * rep0 + r.  A replicate of a contig under a seed is therefore a pure function of (pi, T, E, A, q, N, seed, contig, replicate): not
+ * of how many replicates a call asks for, of how they sit on wavefronts, of `cap`, or of what ran before.
+ *
+ * Arithmetic: fp64 throughout.  Per state the host adds the alphabet's mass in alphabet order, forms s_i and log s_i with the
+ * host's log, and 1 - Ebar(q | i) as the sum over the alphabet WITHOUT q divided by the mass (no cancellation); the device takes
+ * log(1 - u_0) (1 - u_0 is exact) and the two CDFs (lane-local prefix sums plus a wave scan: not the sequential order).
+ *
+ * A call draws at most `cap` events per replicate.  Outputs, all [n_contigs x nreps] row-major in front: x0 = x_0 where this call
+ * drew it, else -1; n_events = loud positions written by this call; pos (int64), state, key (int32) [.. x cap]: position, state and
+ * ALPHABET index of each loud position, ascending (entries beyond n_events are unspecified); resume_out [.. x 3] =
+ * (next event index, position reached, state there).  A replicate is finished when its position equals N.  resume_in (NULL: every
+ * replicate starts at (0, 0, -1) = nothing drawn yet) takes what an earlier call returned in resume_out: a run continued through
+ * any sequence of caps gives the bits of an uncapped one.
+ * The call fails before anything is launched when: the parameters are not set; a length < 1, nreps < 1 or cap < 1; an alphabet
+ * index is out of range or given twice; quiet is not in the alphabet; a state gives the alphabet no mass; rep0 < 0 or
+ * rep0 + nreps > 2^31; contig0 < 0 or contig0 + n_contigs > 2^32; n_contigs x nreps x cap > 2^31 - 1; a resume state that no call
+ * can have returned.  With every output pointer NULL the call runs these checks alone.  The parameters are prepared if need be (as
+ * smcpp_q does); no E-step is needed, and none is disturbed. */
+int smcpp_simulate(smcpp_im *im, int n_contigs, const long long *lengths, int n_alpha, const int *alpha_keys, int quiet,
+                   unsigned long long seed, long long contig0, long long rep0, long long nreps, long long cap,
+                   const long long *resume_in /* [n_contigs x nreps x 3] or NULL */, int *x0, long long *n_events,
+                   long long *pos, int *state, int *key, long long *resume_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,6 +310,48 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_posterior_windows_exact(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
         return out
 
+    def _hmm_tables(self):
+        """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""
+        K = E.lib().smcpp_num_keys(self._im)
+        pi, T, Et = np.zeros(self.M), np.zeros((self.M, self.M)), np.zeros((K, self.M))
+        E.check(E.lib().smcpp_get_pi(self._im, E.dptr(pi)))
+        E.check(E.lib().smcpp_get_transition(self._im, E.dptr(T)))
+        E.check(E.lib().smcpp_get_emission_probs(self._im, E.dptr(Et)))
+        return pi, T, Et
+
+    def _simulate_call(self, lengths, alphabet, quiet, seed, contig0, rep0, nreps, cap, resume):
+        """One `smcpp_simulate` call: -> (x0 [nc, R], n_events [nc, R], pos [nc, R, cap], state, key, resume_out [nc, R, 3])."""
+        lengths = aca(lengths, dtype=np.int64).reshape(-1)
+        alphabet = aca(alphabet, dtype=np.int32).reshape(-1)
+        nc, R, cap = len(lengths), int(nreps), int(cap)
+        shape = (nc, max(R, 0))
+        ll = C.POINTER(C.c_longlong)
+        rin = None if resume is None else aca(resume, dtype=np.int64).reshape(-1)
+        args = (self._im, nc, lengths.ctypes.data_as(ll), len(alphabet), E.iptr(alphabet), int(quiet), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                int(contig0), int(rep0), R, cap, None if rin is None else rin.ctypes.data_as(ll))
+        E.check(E.lib().smcpp_simulate(*args, None, None, None, None, None, None))     # (the checks alone: nothing is allocated for a bad call)
+        x0 = np.empty(shape, dtype=np.int32)
+        nev = np.empty(shape, dtype=np.int64)
+        pos = np.empty(shape + (cap,), dtype=np.int64)
+        state = np.empty(shape + (cap,), dtype=np.int32)
+        key = np.empty(shape + (cap,), dtype=np.int32)
+        rout = np.empty(shape + (3,), dtype=np.int64)
+        E.check(E.lib().smcpp_simulate(*args, E.iptr(x0), nev.ctypes.data_as(ll), pos.ctypes.data_as(ll), E.iptr(state), E.iptr(key),
+                                       rout.ctypes.data_as(ll)))
+        return x0, nev, pos, state, key, rout
+
+    def simulate(self, lengths, n_replicates=1, seed=0, alphabet=None, quiet=None, first_replicate=0, first_contig=0, cap=None):
+        """Draw `n_replicates` data sets with their hidden paths from the model this manager holds, on the device: one simulated
+        contig of `lengths[c]` positions per entry (include/smcpp_engine.h: smcpp_simulate states the process, the event-driven
+        walk and the random stream).  `alphabet`: key indices (rows of `keys`; default: all of them), `quiet`: the key index of
+        the monomorphic observation (default: the alphabet's key with a = b = 0 and the most observed lineages).  Returns a dict:
+        `x0` int32 `[contigs, replicates]`, and `pos` (int64), `state`, `key` (int32; the index INTO the alphabet) as
+        `[contig][replicate]` lists of arrays over the loud positions, ascending.  Replicate `first_replicate + r` of contig
+        `first_contig + c` under `seed` is the same whatever else a call asks for and whatever `cap` (events per replicate and
+        device call; default: sized from the model) is."""
+        from .simulate import drive
+        return drive(self, lengths, n_replicates, seed, alphabet, quiet, first_replicate, first_contig, cap)
+
     @property
     def xisums(self):
         ret = []

@@ -116,6 +116,7 @@ cdef extern from "smcpp_engine.h":
     int smcpp_posterior_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, double *out) nogil
     int smcpp_posterior_position_summary(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, const double *weights, int nq, const double *q, int *argmax, double *mean, int *qstate) nogil
     int smcpp_posterior_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
+    int smcpp_simulate(smcpp_im *im, int n_contigs, const long long *lengths, int n_alpha, const int *alpha_keys, int quiet, unsigned long long seed, long long contig0, long long rep0, long long nreps, long long cap, const long long *resume_in, int *x0, long long *n_events, long long *pos, int *state, int *key, long long *resume_out) nogil
 # --- end generated ---
 
 aca = np.ascontiguousarray
@@ -558,6 +559,53 @@ cdef class _PyInferenceManager:
             rc = smcpp_posterior_windows_exact(self._im, cc, W, &nw, op)
         _check(rc)
         return out[:, :nw] if nw < out.shape[1] else out
+
+    def _hmm_tables(self):
+        """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""
+        cdef int M = len(self._hs) - 1, K = smcpp_num_keys(self._im)
+        cdef np.ndarray[double, ndim=1] pi = np.zeros(M)
+        cdef np.ndarray[double, ndim=2] T = np.zeros((M, M)), Et = np.zeros((max(K, 1), M))
+        _check(smcpp_get_pi(self._im, &pi[0]))
+        _check(smcpp_get_transition(self._im, &T[0, 0]))
+        _check(smcpp_get_emission_probs(self._im, &Et[0, 0]))
+        return pi, T, Et[:K]
+
+    def _simulate_call(self, lengths, alphabet, quiet, seed, contig0, rep0, nreps, cap, resume):
+        """One `smcpp_simulate` call: -> (x0 [nc, R], n_events [nc, R], pos [nc, R, cap], state, key, resume_out [nc, R, 3])."""
+        cdef np.ndarray[long long, ndim=1] ln = aca(np.asarray(lengths, dtype=np.int64).reshape(-1)), rin
+        cdef np.ndarray[int, ndim=1] al = aca(np.asarray(alphabet, dtype=np.int32).reshape(-1))
+        cdef int nc = len(ln), na = len(al), q = quiet, rc
+        cdef unsigned long long sd = int(seed) & 0xFFFFFFFFFFFFFFFF
+        cdef long long c0 = contig0, r0 = rep0, R = nreps, cp = cap
+        cdef long long *lp = &ln[0] if nc > 0 else NULL
+        cdef int *ap = &al[0] if na > 0 else NULL
+        cdef long long *rp = NULL
+        if resume is not None:
+            rin = aca(np.asarray(resume, dtype=np.int64).reshape(-1))
+            rp = &rin[0]
+        with nogil:
+            rc = smcpp_simulate(self._im, nc, lp, na, ap, q, sd, c0, r0, R, cp, rp, NULL, NULL, NULL, NULL, NULL, NULL)      # (the checks alone)
+        _check(rc)
+        cdef long long units = nc * R, cells = units * cp
+        cdef np.ndarray[int, ndim=1] x0 = np.empty(units, dtype=np.int32), state = np.empty(cells, dtype=np.int32), key = np.empty(cells, dtype=np.int32)
+        cdef np.ndarray[long long, ndim=1] nev = np.empty(units, dtype=np.int64), pos = np.empty(cells, dtype=np.int64), rout = np.empty(3 * units, dtype=np.int64)
+        cdef int *x0p = &x0[0]
+        cdef int *stp = &state[0]
+        cdef int *kp = &key[0]
+        cdef long long *nevp = &nev[0]
+        cdef long long *posp = &pos[0]
+        cdef long long *routp = &rout[0]
+        with nogil:
+            rc = smcpp_simulate(self._im, nc, lp, na, ap, q, sd, c0, r0, R, cp, rp, x0p, nevp, posp, stp, kp, routp)
+        _check(rc)
+        return (x0.reshape(nc, R), nev.reshape(nc, R), pos.reshape(nc, R, cp), state.reshape(nc, R, cp), key.reshape(nc, R, cp),
+                rout.reshape(nc, R, 3))
+
+    def simulate(self, lengths, n_replicates=1, seed=0, alphabet=None, quiet=None, first_replicate=0, first_contig=0, cap=None):
+        """Draw data sets with their hidden paths from the model this manager holds (`_smcpp.py`: simulate; include/smcpp_engine.h:
+        smcpp_simulate)."""
+        from .simulate import drive
+        return drive(self, lengths, n_replicates, seed, alphabet, quiet, first_replicate, first_contig, cap)
 
     property xisums:
         def __get__(self):

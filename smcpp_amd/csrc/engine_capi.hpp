@@ -706,6 +706,126 @@ int smcpp_posterior_sample_positions(smcpp_im *im, int c, unsigned long long see
     API_END
 }
 
+// ---- simulation (simulate_dev.hpp) ----
+int smcpp_simulate(smcpp_im *im, int n_contigs, const long long *lengths, int n_alpha, const int *alpha_keys, int quiet,
+                   unsigned long long seed, long long contig0, long long rep0, long long nreps, long long cap,
+                   const long long *resume_in, int *x0, long long *n_events, long long *pos, int *state, int *key,
+                   long long *resume_out) {
+    API_BEGIN
+    // ---- the arguments: every refusal before anything is launched ----
+    if (n_contigs < 1 || !lengths) throw std::runtime_error("simulate: no contig lengths");
+    for (int c = 0; c < n_contigs; ++c)
+        if (lengths[c] < 1) throw std::runtime_error("simulate: contig " + std::to_string(c) + " has N < 1 positions");
+    if (nreps < 1) throw std::runtime_error("simulate: n_replicates < 1");
+    if (cap < 1) throw std::runtime_error("simulate: cap < 1 (events per replicate and call)");
+    if (rep0 < 0) throw std::runtime_error("simulate: first_replicate < 0");
+    if (rep0 > (1LL << 31) || nreps > (1LL << 31) || rep0 + nreps > (1LL << 31))
+        throw std::runtime_error("simulate: first_replicate + n_replicates > 2^31 (the replicate index is one 32-bit word of the counter)");
+    if (contig0 < 0 || contig0 + n_contigs > (1LL << 32))
+        throw std::runtime_error("simulate: the contig index does not fit one 32-bit word of the counter");
+    if (n_alpha < 1 || !alpha_keys) throw std::runtime_error("simulate: the alphabet is empty");
+    const int M = im->M, K = im->K, A = n_alpha;
+    std::vector<unsigned char> seen(K, 0);
+    int qa = -1;
+    for (int k = 0; k < A; ++k) {
+        const int id = alpha_keys[k];
+        if (id < 0 || id >= K)
+            throw std::runtime_error("simulate: alphabet entry " + std::to_string(k) + " (key index " + std::to_string(id) +
+                                     ") is out of range: the manager holds " + std::to_string(K) + " keys");
+        if (seen[id]) throw std::runtime_error("simulate: key index " + std::to_string(id) + " is given twice in the alphabet");
+        seen[id] = 1;
+        if (id == quiet) qa = k;
+    }
+    if (qa < 0) throw std::runtime_error("simulate: the quiet key (key index " + std::to_string(quiet) + ") is not in the alphabet");
+    const long long units = (long long)n_contigs * nreps;
+    if (units > ((1LL << 31) - 1) / cap)
+        throw std::runtime_error("simulate: the outputs (" + std::to_string(n_contigs) + " contigs x " + std::to_string(nreps) +
+                                 " replicates x " + std::to_string(cap) + " events) exceed the cap of 2^31 - 1 elements per call: ask "
+                                 "for fewer replicates or a smaller cap");
+    if (resume_in)
+        for (long long u = 0; u < units; ++u) {
+            const long long e = resume_in[3 * u], p = resume_in[3 * u + 1], i = resume_in[3 * u + 2], N = lengths[u / nreps];
+            const bool fresh = i == -1 && e == 0 && p == 0;
+            if (!fresh && (e < 0 || e > (1LL << 60) || p < 0 || p > N || i < 0 || i >= M))
+                throw std::runtime_error("simulate: resume state " + std::to_string(u) + " is not one a call has returned for this contig");
+        }
+    // ---- the parameters ----
+    if (!im->have_raw && !im->have_model) throw std::runtime_error("simulate: parameters are not set (set_params or set_raw first)");
+    if (!im->have_raw) im->prepare_params();
+    im->sync_host_E();
+    im->ensure_T();
+    if ((int)im->pi.size() != M || (int)im->T.size() != M * M || im->E.size() != (size_t)K * M)
+        throw std::runtime_error("simulate: parameters are not set (set_params or set_raw first)");
+    const int NPL = im->NPL, MS = 64 * NPL;
+    // per state: the alphabet's mass, s_i = T(i, i) Ebar(q | i), the weight of staying on a loud key (added up without the quiet
+    // entry: no cancellation in 1 - Ebar(q | i))
+    std::vector<double> EA((size_t)M * A), vec((size_t)2 * M + MS, 0.0), Tp((size_t)M * MS, 0.0);
+    for (int m = 0; m < M; ++m) {
+        double mass = 0.0, loud = 0.0;
+        for (int k = 0; k < A; ++k) {
+            const double v = im->E[(size_t)alpha_keys[k] * M + m];
+            if (!(v >= 0.0) || !std::isfinite(v))
+                throw std::runtime_error("simulate: the emission probability of alphabet entry " + std::to_string(k) + " in state " +
+                                         std::to_string(m) + " is negative or not finite");
+            EA[(size_t)m * A + k] = v;
+            mass += v;
+            if (k != qa) loud += v;
+        }
+        if (!(mass > 0.0))
+            throw std::runtime_error("simulate: state " + std::to_string(m) + " gives the alphabet no mass: no observation can be drawn there");
+        const double tii = im->T[(size_t)m * M + m];
+        const double s = tii * (EA[(size_t)m * A + qa] / mass);
+        vec[m] = s > 0.0 ? std::log(s) : -INFINITY;
+        vec[(size_t)M + m] = tii * (loud / mass);
+        vec[(size_t)2 * M + m] = im->pi[m];
+        std::memcpy(&Tp[(size_t)m * MS], &im->T[(size_t)m * M], sizeof(double) * M);
+    }
+    if (!x0 && !n_events && !pos && !state && !key && !resume_out) return 0;          // (the checks alone)
+    if (!x0 || !n_events || !pos || !state || !key || !resume_out) throw std::runtime_error("simulate: an output array is missing");
+    // ---- the launch: one persistent wavefront per (contig, replicate), as many as there are wavefront slots ----
+    HIPCHK(hipSetDevice(im->device));
+    hipStream_t s = im->stream;
+    const std::vector<long long> len(lengths, lengths + n_contigs);
+    im->d_sim_T.upload(Tp, s); im->d_sim_EA.upload(EA, s); im->d_sim_vec.upload(vec, s); im->d_sim_len.upload(len, s);
+    if (resume_in) {
+        im->d_sim_rin.alloc((size_t)3 * units);
+        HIPCHK(hipMemcpyAsync(im->d_sim_rin.p, resume_in, sizeof(long long) * 3 * units, hipMemcpyHostToDevice, s));
+    }
+    const size_t cells = (size_t)units * (size_t)cap;
+    im->d_sim_x0.alloc((size_t)units); im->d_sim_nev.alloc((size_t)units); im->d_sim_rout.alloc((size_t)3 * units);
+    im->d_sim_pos.alloc(cells); im->d_sim_state.alloc(cells); im->d_sim_key.alloc(cells);
+    SimArgs sa;
+    sa.M = M; sa.MS = MS; sa.A = A; sa.q = qa;
+    sa.T = im->d_sim_T.p; sa.EA = im->d_sim_EA.p; sa.ls = im->d_sim_vec.p; sa.wst = im->d_sim_vec.p + M; sa.pi = im->d_sim_vec.p + 2 * (size_t)M;
+    sa.len = im->d_sim_len.p;
+    sa.k0 = (unsigned)(seed & 0xffffffffull); sa.k1 = (unsigned)(seed >> 32) ^ 0x53494D55u;
+    sa.contig0 = (unsigned)contig0;
+    sa.rep0 = rep0; sa.nreps = nreps; sa.units = units; sa.cap = cap;
+    sa.resume_in = resume_in ? im->d_sim_rin.p : nullptr;
+    sa.x0 = im->d_sim_x0.p; sa.nev = im->d_sim_nev.p; sa.pos = im->d_sim_pos.p; sa.state = im->d_sim_state.p; sa.key = im->d_sim_key.p;
+    sa.resume_out = im->d_sim_rout.p;
+    const long long slots = NPL >= 8 ? 1024 : 4096;
+    const int nw = (int)std::min(units, slots);
+    im->sim_waves = nw; im->sim_units = units; im->sim_events = 0;
+    const dim3 grid(ceil_div(nw, 4)), block(256);
+    switch (NPL) {
+#define SIM_(x) case x: hipLaunchKernelGGL((k_simulate<x>), grid, block, 0, s, sa, nw); break;
+        SIM_(1) SIM_(2) SIM_(3) SIM_(4) SIM_(8)
+        default: SIM_(16)
+#undef SIM_
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(x0, im->d_sim_x0.p, sizeof(int) * units, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_events, im->d_sim_nev.p, sizeof(long long) * units, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(resume_out, im->d_sim_rout.p, sizeof(long long) * 3 * units, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pos, im->d_sim_pos.p, sizeof(long long) * cells, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(state, im->d_sim_state.p, sizeof(int) * cells, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(key, im->d_sim_key.p, sizeof(int) * cells, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));                   // (the staged tables are locals: the copies have to be done before they go)
+    for (long long u = 0; u < units; ++u) im->sim_events += n_events[u];
+    API_END
+}
+
 // ---- posterior positions (posterior_pos_dev.hpp) ----
 // Positions 0 .. N of contig c; engine row i covers positions q0 + 1 .. q0 + span.  The item table of a grid: the engine rows that
 // hold a grid position, ascending - a caller's row of ONE position (and position 0) as a stored item, every other one to walk.

@@ -226,6 +226,13 @@ struct smcpp_im {
     // rows: [3][npaths][ncols] of the selection (ncols > 0), pos: [npaths][pos1 - pos0] (pos1 > pos0), on the device, on `stream`
     PostPaths post_paths(int c, unsigned long long seed, long long path0, long long npaths, long long start, long long step,
                          long long ncols, long long pos0, long long pos1);
+    // simulation (simulate_dev.hpp, smcpp_simulate): the padded dense T, the alphabet's emission table by state, the per-state
+    // vectors (log s | stay-loud weight | pi), the contig lengths, the resume triples and the per-replicate outputs
+    DevBuf<double> d_sim_T, d_sim_EA, d_sim_vec;
+    DevBuf<long long> d_sim_len, d_sim_rin, d_sim_rout, d_sim_nev, d_sim_pos;
+    DevBuf<int> d_sim_x0, d_sim_state, d_sim_key;
+    int sim_waves = 0;                            // wavefronts of the last simulate call (smcpp_describe)
+    long long sim_units = 0, sim_events = 0;      // its (contig, replicate) pairs and the loud positions it wrote
     // posterior positions (posterior_pos_dev.hpp, smcpp_posterior_positions / _position_summary / _windows_exact): the item table of
     // the last call (engine rows to walk, positions whose marginal is stored), the wavefronts' scratch, the segment sums of the
     // rows a window boundary cuts

@@ -259,6 +259,9 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         s += ", \"path_waves\": " + std::to_string(im->pp_waves) + ", \"transition_waves\": " + std::to_string(im->pt_waves);
         // ... and of the last posterior position call: its wavefronts and the engine rows it walked
         s += ", \"position_waves\": " + std::to_string(im->pq_waves) + ", \"position_rows_walked\": " + std::to_string(im->pq_walked);
+        // ... and of the last simulate call: its wavefronts, its (contig, replicate) pairs and the loud positions it wrote
+        s += ", \"simulate_waves\": " + std::to_string(im->sim_waves) + ", \"simulate_units\": " + std::to_string(im->sim_units);
+        s += ", \"simulate_events\": " + std::to_string(im->sim_events);
     }
     s += "}";
     if (buf && cap > 0) {
