@@ -440,6 +440,38 @@ int smcpp_posterior_position_summary(smcpp_im *im, int contig, long long pos0, l
 int smcpp_posterior_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
                                   double *out /* [M x n_windows] row-major; NULL: only n_windows */);
 
+/* ---- log-likelihood track (loglik_track_dev.hpp): WHERE along contig c the log-likelihood of the last E-step comes from.  The
+ * reference keeps one number per row, HMM::log_c (hmm.h; filled by HMM::forward_backward and only ever summed, HMM::loglik); the
+ * three entries extend that interface.  Conventions as for the posterior positions: caller's rows l = 1 .. L with spans s_l,
+ * P_l = s_1 + .. + s_l, positions 0 .. N with N = P_L; position 0 carries no observation.
+ *     l(p) = log P(o_1 .. o_p),   l(0) = 0,   l(P_l) = sum_{r <= l} log c_r  (the engine's own per-row values; a caller's row the
+ *     engine cut into pieces is the sum of its pieces), so l(N) is what smcpp_loglik reports for the contig.
+ * Inside an engine row r of span s that starts behind position p0, with e the emission vector of its key: x_0 = the stored float
+ * forward vector in front of the row, normalised; x_q ~ e o (T^T x_{q-1}); z_q = the sum of e o (T^T x_{q-1}) for normalised
+ * x_{q-1}; A_q = sum_{t <= q} log z_t (fp64) and
+ *     l(p0 + q) = l(p0) + log c_r  A_q / A_s:
+ * the walk splits the row's stored log c in the proportions of its own running sum, so l is continuous at row ends, does not
+ * increase wherever log c_r <= 0, and windows add up to the contig's log-likelihood whatever the float start vector did to A_s.
+ * A value is a pure function of the stored vectors and the position: not of the grid, the launch shape (SMCPP_LL_WAVES), the call
+ * order or what ran before.  smcpp_describe reports "ll_items" (engine rows walked), "ll_waves" and "ll_walk_worst_ratio", the
+ * worst |A_s / log c_r - 1| of the last call.
+ * Preconditions: an E-step has been run and the parameters have not been set since - a PLAIN one is enough (save_gamma is not
+ * needed: every E-step plan leaves the forward vector and log c of every engine row in memory), and the posterior buffers are
+ * neither needed nor disturbed; _positions and _windows also need a transition matrix with the model's semiseparable structure
+ * (as smcpp_posterior_transitions); a valid selection / grid, window_bp >= 1, at most 2^31 - 1 output elements.  Every failure
+ * happens before anything is launched and leaves the manager usable.  out == NULL runs the checks alone.
+ *
+ * smcpp_loglik_rows (extends HMM::log_c, hmm.h): log c of the caller's rows of the selection range(start, stop, step) over
+ * 0 .. L, the selection rule of smcpp_posterior_summary; row 0 gives 0, as log_c[0] does in the reference. */
+int smcpp_loglik_rows(smcpp_im *im, int contig, long long start, long long stop, long long step, double *out /* [ncols] */);
+/* smcpp_loglik_positions (extends HMM::log_c, hmm.h, below the row): l on the grid pos0, pos0 + step, .. < pos1 of 0 .. N,
+ * 0 <= pos0 < pos1 <= N + 1. */
+int smcpp_loglik_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, double *out /* [npos] */);
+/* smcpp_loglik_windows (extends HMM::log_c, hmm.h, to windows of base pairs): out[w] = l(min((w + 1) W, N)) - l(w W) for
+ * w = 0 .. ceil(N / W) - 1; the windows sum to the contig's log-likelihood. */
+int smcpp_loglik_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
+                         double *out /* [n_windows]; NULL: only n_windows */);
+
 /* ---- simulation (simulate_dev.hpp): draws of (hidden path, observations) from the model the manager holds - the process whose
  * marginal likelihood the E-step computes.  A simulated contig has positions 1 .. N; position 0 is column 0 and carries no
  * observation:

@@ -310,6 +310,34 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_posterior_windows_exact(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
         return out
 
+    def loglik_rows(self, c=0, start=0, stop=None, step=1):
+        """`[ncols]`: log c of the caller's rows `range(start, stop, step)` of contig `c` under the last E-step (a plain one is
+        enough); row 0 gives 0 and the rows sum to `logliks()[c]`.  (include/smcpp_engine.h: smcpp_loglik_rows.)"""
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        E.check(E.lib().smcpp_loglik_rows(self._im, int(c), start, stop, step, None))              # (the checks alone)
+        out = np.empty(ncols)
+        E.check(E.lib().smcpp_loglik_rows(self._im, int(c), start, stop, step, E.dptr(out)))
+        return out
+
+    def loglik_positions(self, c=0, pos0=0, pos1=None, step=1):
+        """`[npos]`: `l(p) = log P(o_1 .. o_p)` at the positions `range(pos0, pos1, step)` of `0 .. P_L` of contig `c` (position 0
+        carries no observation: `l(0) = 0`; `l(P_L)` is `logliks()[c]`).  Inside a row the engine walks forward from the stored
+        vector and splits the row's log c exactly.  (include/smcpp_engine.h: smcpp_loglik_positions.)"""
+        c, pos0, pos1, step, npos = self._grid(c, pos0, pos1, step)
+        E.check(E.lib().smcpp_loglik_positions(self._im, c, pos0, pos1, step, None))               # (the checks alone)
+        out = np.empty(npos)
+        E.check(E.lib().smcpp_loglik_positions(self._im, c, pos0, pos1, step, E.dptr(out)))
+        return out
+
+    def loglik_windows(self, c=0, window=10_000):
+        """`[ceil(P_L / window)]`: the log-likelihood of contig `c` per window of `window` positions,
+        `l(min((w + 1) W, P_L)) - l(w W)`; the windows sum to `logliks()[c]`.  (include/smcpp_engine.h: smcpp_loglik_windows.)"""
+        nw = C.c_longlong(0)
+        E.check(E.lib().smcpp_loglik_windows(self._im, int(c), int(window), C.byref(nw), None))
+        out = np.empty(nw.value)
+        E.check(E.lib().smcpp_loglik_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
+        return out
+
     def _hmm_tables(self):
         """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""
         K = E.lib().smcpp_num_keys(self._im)

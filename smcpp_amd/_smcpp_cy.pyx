@@ -116,6 +116,9 @@ cdef extern from "smcpp_engine.h":
     int smcpp_posterior_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, double *out) nogil
     int smcpp_posterior_position_summary(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, const double *weights, int nq, const double *q, int *argmax, double *mean, int *qstate) nogil
     int smcpp_posterior_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
+    int smcpp_loglik_rows(smcpp_im *im, int contig, long long start, long long stop, long long step, double *out) nogil
+    int smcpp_loglik_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, double *out) nogil
+    int smcpp_loglik_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
     int smcpp_simulate(smcpp_im *im, int n_contigs, const long long *lengths, int n_alpha, const int *alpha_keys, int quiet, unsigned long long seed, long long contig0, long long rep0, long long nreps, long long cap, const long long *resume_in, int *x0, long long *n_events, long long *pos, int *state, int *key, long long *resume_out) nogil
 # --- end generated ---
 
@@ -559,6 +562,45 @@ cdef class _PyInferenceManager:
             rc = smcpp_posterior_windows_exact(self._im, cc, W, &nw, op)
         _check(rc)
         return out[:, :nw] if nw < out.shape[1] else out
+
+    def loglik_rows(self, c=0, start=0, stop=None, step=1):
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        cdef int cc = c, rc
+        cdef long long a = start, b = stop, st = step
+        with nogil:
+            rc = smcpp_loglik_rows(self._im, cc, a, b, st, NULL)                                     # (the checks alone)
+        _check(rc)
+        cdef np.ndarray[double, ndim=1] out = np.empty(max(ncols, 1))
+        cdef double *op = &out[0]
+        with nogil:
+            rc = smcpp_loglik_rows(self._im, cc, a, b, st, op)
+        _check(rc)
+        return out[:ncols] if ncols < out.shape[0] else out
+
+    def loglik_positions(self, c=0, pos0=0, pos1=None, step=1):
+        pos0, pos1, step, npos = self._grid(c, pos0, pos1, step)
+        cdef int cc = c, rc
+        cdef long long a = pos0, b = pos1, st = step
+        with nogil:
+            rc = smcpp_loglik_positions(self._im, cc, a, b, st, NULL)                                # (the checks alone)
+        _check(rc)
+        cdef np.ndarray[double, ndim=1] out = np.empty(max(npos, 1))
+        cdef double *op = &out[0]
+        with nogil:
+            rc = smcpp_loglik_positions(self._im, cc, a, b, st, op)
+        _check(rc)
+        return out[:npos] if npos < out.shape[0] else out
+
+    def loglik_windows(self, c=0, window=10_000):
+        cdef int cc = c, rc
+        cdef long long W = window, nw = 0
+        _check(smcpp_loglik_windows(self._im, cc, W, &nw, NULL))
+        cdef np.ndarray[double, ndim=1] out = np.empty(max(nw, 1))
+        cdef double *op = &out[0]
+        with nogil:
+            rc = smcpp_loglik_windows(self._im, cc, W, &nw, op)
+        _check(rc)
+        return out[:nw] if nw < out.shape[0] else out
 
     def _hmm_tables(self):
         """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""

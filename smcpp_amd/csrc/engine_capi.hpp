@@ -1073,6 +1073,203 @@ int smcpp_posterior_windows_exact(smcpp_im *im, int c, long long window_bp, long
     API_END
 }
 
+// ---- log-likelihood track (loglik_track_dev.hpp) ----
+// Every E-step plan leaves the float alpha and log c of every engine row in memory (the statistics read both), so a plain E-step
+// is enough; `walk`: the call steps through the interior of rows and needs the generators of a structured T as well.
+static void ll_need_estep(smcpp_im *im, int c, bool walk) {
+    if (!im->estep_done) throw std::runtime_error("loglik track: no E-step has been run on this manager yet");
+    if (c < 0 || c >= im->n_contigs) throw std::runtime_error("contig index out of range");
+    if (walk) im->post_transitions_check();
+    else if (im->dirty)
+        throw std::runtime_error("loglik track: the parameters were set again after the last E-step, whose stored values belong to the "
+                                 "earlier ones: run the E-step again");
+}
+
+// The position prefix of the engine's rows of contig c: the caller's where no row is cut.
+const long long *smcpp_im::ll_epos_dev(int c) {
+    if (!split_spans) {
+        if (d_user_prefix.size() != (size_t)n_contigs) d_user_prefix.resize(n_contigs);
+        if (!d_user_prefix[c].p) {
+            d_user_prefix[c].upload(user_prefix[c], stream);               // (a member: it outlives the copy)
+            HIPCHK(hipStreamSynchronize(stream));
+        }
+        return d_user_prefix[c].p;
+    }
+    if (d_ll_epos.size() != (size_t)n_contigs) d_ll_epos.resize(n_contigs);
+    if (!d_ll_epos[c].p) {
+        const int Le = Ls[c];
+        std::vector<long long> ep((size_t)Le + 1, 0);
+        for (int i = 1; i <= Le; ++i) {
+            const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+            ep[i] = ep[i - 1] + (ri.gid >= 0 ? groups[ri.gid].span : 1);
+        }
+        d_ll_epos[c].upload(ep, stream);
+        HIPCHK(hipStreamSynchronize(stream));          // (`ep` is a local: the copy has to be done before it goes)
+    }
+    return d_ll_epos[c].p;
+}
+
+// pre[i] = sum of log c over the engine rows 1 .. i of contig c, pre[0] = 0: block sums, one block over them, downsweep
+const double *smcpp_im::ll_prefix(int c) {
+    HIPCHK(hipSetDevice(device));
+    const long long Le = Ls[c];
+    const int nb = std::max(1, ceil_div(Le, LL_SCAN_BLOCK));
+    const double *v = d_logc.p + (size_t)contig_base[c];
+    d_ll_part.alloc((size_t)nb);
+    d_ll_pre.alloc((size_t)Le + 1);
+    hipLaunchKernelGGL(k_ll_scan_partials, dim3(nb), dim3(LL_SCAN_BLOCK), 0, stream, Le, v, d_ll_part.p);
+    hipLaunchKernelGGL(k_ll_scan_of_partials, dim3(1), dim3(LL_SCAN_BLOCK), 0, stream, (long long)nb, d_ll_part.p);
+    hipLaunchKernelGGL(k_ll_scan_down, dim3(nb), dim3(LL_SCAN_BLOCK), 0, stream, Le, v, (const double *)d_ll_part.p, d_ll_pre.p);
+    HIPCHK(hipGetLastError());
+    return d_ll_pre.p;
+}
+
+// The item table: the engine rows with a query position STRICTLY inside, ascending.  Grid: the queries are pos0, pos0 + step, ..
+// < pos1 and query j owns slot j; windows: the queries are the boundaries step, 2 step, .. < N and the slots are counted.
+void smcpp_im::ll_table(int c, long long pos0, long long pos1, long long step, bool windows) {
+    const int Le = Ls[c];
+    ll_items.clear();
+    ll_nslots = 0;
+    long long q0 = 0;
+    for (int i = 1; i <= Le; ++i) {
+        const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+        const int span = ri.gid >= 0 ? groups[ri.gid].span : 1;
+        const long long end = q0 + span;
+        if (q0 + 1 >= pos1) break;
+        if (span > 1 && end - 1 >= pos0) {
+            const long long lo = std::max(q0 + 1, pos0);
+            const long long g = pos0 + (lo - pos0 + step - 1) / step * step;      // the first query behind q0, if any
+            if (g < end && g < pos1) {
+                const long long last = std::min(end - 1, pos1 - 1);
+                const int nq = (int)((last - g) / step + 1);
+                ll_items.push_back(LlItem{q0, g, windows ? ll_nslots : (g - pos0) / step, i, nq});
+                ll_nslots += nq;
+            }
+        }
+        q0 = end;
+    }
+}
+
+void smcpp_im::ll_walk(int c, long long step, double *slots) {
+    const int MS = 64 * NPL;
+    d_ll_gen.upload(ss_gen, stream);                   // (ss_gen is a member: it outlives the copy)
+    SsArgs sa = SsArgs();
+    sa.M = M; sa.Mp = Mp;
+    const double *gd = d_ll_gen.p;
+    sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
+    sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
+    sa.c0 = ss_c0;
+    LlArgs la = LlArgs();
+    la.M = M; la.Mp = Mp; la.nitems = (int)ll_items.size(); la.base = contig_base[c];
+    la.rowinfo = d_rowinfo.p; la.g_span = d_g_span.p; la.E = d_E.p; la.alpha = d_alpha.p; la.logc = d_logc.p; la.pre = d_ll_pre.p;
+    d_ll_items.upload(ll_items, stream);               // (a member: it outlives the copy)
+    d_ll_ratio.alloc((size_t)la.nitems);
+    la.items = d_ll_items.p; la.step = step; la.out = slots; la.ratio = d_ll_ratio.p;
+    // one wavefront per item, persistent: as many as there are wavefront slots, or as SMCPP_LL_WAVES allows
+    long long nw = std::min<long long>(la.nitems, NPL >= 8 ? 1024 : 4096);
+    if (opt().has(smcpp_opt::O_LL_WAVES)) nw = std::min(nw, std::max<long long>(1, opt().ll(smcpp_opt::O_LL_WAVES, 1)));
+    ll_waves = (int)nw;
+    const dim3 grid(ceil_div(nw, 4)), block(256);
+    switch (NPL) {
+#define LL_(x) case x: hipLaunchKernelGGL((k_ll_walk<x>), grid, block, 0, stream, sa, la, (int)nw); break;
+        LL_(1) LL_(2) LL_(3) LL_(4) LL_(8)
+        default: LL_(16)
+#undef LL_
+    }
+    HIPCHK(hipGetLastError());
+    ll_ratio_h.resize((size_t)la.nitems);
+    HIPCHK(hipMemcpyAsync(ll_ratio_h.data(), d_ll_ratio.p, sizeof(double) * la.nitems, hipMemcpyDeviceToHost, stream));
+}
+
+// (behind the stream's synchronisation) the worst ratio of the walk that has just run
+static void ll_close(smcpp_im *im, bool walked) {
+    im->ll_nitems = walked ? (long long)im->ll_items.size() : 0;
+    if (!walked) im->ll_waves = 0;
+    double w = 0.0;
+    if (walked)
+        for (double r : im->ll_ratio_h) w = (r > w || r != r) ? r : w;
+    im->ll_worst = std::isfinite(w) ? w : 1e300;
+}
+
+static void ll_cap(long long n, const char *what) {
+    if (n > (1LL << 31) - 1)
+        throw std::runtime_error(std::string("loglik track: ") + what + " (" + std::to_string(n) + ") exceed the cap of 2^31 - 1 elements "
+                                 "per call: ask for a narrower or a coarser grid, or a wider window");
+}
+
+int smcpp_loglik_rows(smcpp_im *im, int c, long long start, long long stop, long long step, double *out) {
+    API_BEGIN
+    ll_need_estep(im, c, false);
+    const long long ncols = post_check_selection(im, c, start, stop, step);
+    if (!out) return 0;
+    const double *pre = im->ll_prefix(c);              // (selects the device)
+    const int *first = im->piece_first_dev(c);
+    im->d_ll_out.alloc((size_t)ncols);
+    hipLaunchKernelGGL(k_ll_rows, dim3((unsigned)ceil_div(ncols, 256)), dim3(256), 0, im->stream, start, step, ncols, first, pre,
+                       im->d_ll_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, im->d_ll_out.p, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost, im->stream));
+    HIPCHK(hipStreamSynchronize(im->stream));
+    ll_close(im, false);
+    API_END
+}
+
+int smcpp_loglik_positions(smcpp_im *im, int c, long long pos0, long long pos1, long long step, double *out) {
+    API_BEGIN
+    ll_need_estep(im, c, true);
+    const long long N = im->user_prefix[c][im->user_Ls[c]];
+    if (pos0 < 0) throw std::runtime_error("loglik track: pos0 < 0");
+    if (pos1 > N + 1) throw std::runtime_error("loglik track: pos1 > P_L + 1 (the contig has " + std::to_string(N + 1) + " positions)");
+    if (pos0 >= pos1) throw std::runtime_error("loglik track: empty grid (pos0 >= pos1)");
+    if (step < 1) throw std::runtime_error("loglik track: step < 1");
+    const long long npos = (pos1 - pos0 + step - 1) / step;
+    ll_cap(npos, "the grid positions");
+    if (!out) return 0;
+    im->ll_table(c, pos0, pos1, step, false);
+    const double *pre = im->ll_prefix(c);              // (selects the device)
+    const long long *EP = im->ll_epos_dev(c);
+    hipStream_t s = im->stream;
+    im->d_ll_out.alloc((size_t)npos);
+    hipLaunchKernelGGL(k_ll_ends, dim3((unsigned)ceil_div(npos, 256)), dim3(256), 0, s, pos0, step, npos, (long long)im->Ls[c], EP, pre,
+                       im->d_ll_out.p);
+    HIPCHK(hipGetLastError());
+    const bool walked = !im->ll_items.empty();
+    if (walked) im->ll_walk(c, step, im->d_ll_out.p);
+    HIPCHK(hipMemcpyAsync(out, im->d_ll_out.p, sizeof(double) * (size_t)npos, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ll_close(im, walked);
+    API_END
+}
+
+int smcpp_loglik_windows(smcpp_im *im, int c, long long window_bp, long long *n_windows, double *out) {
+    API_BEGIN
+    ll_need_estep(im, c, true);
+    if (window_bp < 1) throw std::runtime_error("loglik track: window_bp < 1");
+    const long long N = im->user_prefix[c][im->user_Ls[c]];
+    const long long nwin = (N + window_bp - 1) / window_bp;
+    if (n_windows) *n_windows = nwin;
+    ll_cap(nwin, "the windows");
+    if (!out) return 0;
+    im->ll_table(c, 0, N, window_bp, true);            // (the boundaries W, 2 W, .. < N)
+    const double *pre = im->ll_prefix(c);              // (selects the device)
+    const long long *EP = im->ll_epos_dev(c);
+    hipStream_t s = im->stream;
+    const bool walked = !im->ll_items.empty();
+    im->d_ll_bnd.alloc(std::max<size_t>(1, (size_t)im->ll_nslots));
+    if (walked) im->ll_walk(c, window_bp, im->d_ll_bnd.p);
+    else im->d_ll_items.alloc(1);
+    im->d_ll_out.alloc(std::max<size_t>(1, (size_t)nwin));
+    if (nwin > 0) {
+        hipLaunchKernelGGL(k_ll_windows, dim3((unsigned)ceil_div(nwin, 256)), dim3(256), 0, s, window_bp, nwin, (long long)im->Ls[c], EP, pre,
+                           (const LlItem *)im->d_ll_items.p, (int)im->ll_items.size(), (const double *)im->d_ll_bnd.p, im->d_ll_out.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, im->d_ll_out.p, sizeof(double) * (size_t)nwin, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    ll_close(im, walked);
+    API_END
+}
+
 int smcpp_gamma_cols(smcpp_im *im, int c) {
     if (c < 0 || c >= im->n_contigs) return -1;
     return im->gamma_valid ? im->user_Ls[c] + 1 : 1;

@@ -251,6 +251,22 @@ struct smcpp_im {
     void post_positions_scratch_check(size_t extra_bytes);                               // throws beyond the 1 GiB cap
     const double *post_colsum(int c, const PostSource &src);                             // [Lu + 1] column sums on the device
     void post_positions_launch(int c, int kind, PqArgs &pa);
+    // log-likelihood track (loglik_track_dev.hpp, smcpp_loglik_rows / _positions / _windows): buffers of its own - the posterior
+    // products' are neither read nor written.  The position prefix of the ENGINE's rows per contig (where rows are cut; otherwise the
+    // caller's prefix serves), the prefix of log c over one contig's engine rows, the item table of the last call, its outputs
+    std::vector<DevBuf<long long>> d_ll_epos;
+    std::vector<LlItem> ll_items;
+    DevBuf<LlItem> d_ll_items;
+    DevBuf<double> d_ll_gen, d_ll_part, d_ll_pre, d_ll_out, d_ll_bnd, d_ll_ratio;
+    std::vector<double> ll_ratio_h;
+    long long ll_nslots = 0;                      // slots the items of the last table write
+    int ll_waves = 0;                             // wavefronts of the last walk (smcpp_describe)
+    long long ll_nitems = 0;                      // its items
+    double ll_worst = 0.0;                        // the worst |A_span / log c_r - 1| of the last call
+    const long long *ll_epos_dev(int c);          // EP [Le + 1] on the device
+    const double *ll_prefix(int c);               // pre [Le + 1] on the device, on `stream`
+    void ll_table(int c, long long pos0, long long pos1, long long step, bool windows);   // -> ll_items, ll_nslots (host)
+    void ll_walk(int c, long long step, double *slots);                                   // k_ll_walk over ll_items (not empty)
     // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;

@@ -262,6 +262,10 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // ... and of the last simulate call: its wavefronts, its (contig, replicate) pairs and the loud positions it wrote
         s += ", \"simulate_waves\": " + std::to_string(im->sim_waves) + ", \"simulate_units\": " + std::to_string(im->sim_units);
         s += ", \"simulate_events\": " + std::to_string(im->sim_events);
+        // ... and of the last log-likelihood track call: the engine rows it walked, its wavefronts and how far the walk of a row
+        // from the stored float vector moved the row's evidence at worst, |A_span / log c_r - 1|
+        snprintf(t, sizeof t, ", \"ll_items\": %lld, \"ll_waves\": %d, \"ll_walk_worst_ratio\": %.6g", im->ll_nitems, im->ll_waves, im->ll_worst);
+        s += t;
     }
     s += "}";
     if (buf && cap > 0) {

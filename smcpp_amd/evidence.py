@@ -1,0 +1,74 @@
+"""The evidence side of a fit, below the contig level: the log-likelihood per window of positions (`im.loglik_windows`,
+include/smcpp_engine.h: smcpp_loglik_windows), the comparison of two fits of the same data with a block jackknife, and surprisal
+per base pair.  The reference reports one number per contig (`HMM::loglik`, hmm.h); its `cv` scores whole contigs for that reason."""
+from __future__ import annotations
+
+import numpy as np
+
+from .posterior import _decode_setup
+
+
+def loglik_track(model, contigs, M, n, theta, rho, window, alpha=1.0, polarization_error=0.5, a=None, device=-1, return_manager=False):
+    """The log-likelihood of every contig under `model`, per window of `window` positions.  `M` is the number of hidden states
+    (balanced under the model, as `posterior_products` does) or the array of hidden-state break points itself - pass the same
+    array for two models whose tracks are to be compared.  One manager, set up as `posterior_products` sets it up (one or two
+    populations, the missing row in front of every contig: window w covers the caller's base pairs [w W - 1, (w + 1) W - 1)), and
+    ONE PLAIN E-step: the track is a forward-only product and needs no `save_gamma`.
+    Returns `(hidden_states, track)`, `track[c]` the `[ceil(P_c / window)]` window values of contig c; they sum to the contig's
+    log-likelihood.  `return_manager=True` appends the inference manager."""
+    hidden_states = None if np.isscalar(M) else np.asarray(M, dtype=float)
+    nstates = int(M) if hidden_states is None else len(hidden_states) - 1
+    hs, obs, im = _decode_setup(model, contigs, nstates, n, theta, rho, alpha, polarization_error, hidden_states, device, a, None, None, 1,
+                                save_gamma=False)
+    track = [im.loglik_windows(c, int(window)) for c in range(len(obs))]
+    if return_manager:
+        return hs, track, im
+    return hs, track
+
+
+def compare_tracks(track_a, track_b, block=1):
+    """Two window tracks of the SAME data and window under two models -> dict of
+      `delta`   D = sum_b d_b, the difference of the log-likelihoods (a minus b);
+      `se`      sqrt(B / (B - 1) sum_b (d_b - D / B)^2): the delete-one-block jackknife standard error of a sum;
+      `z`       D / se;
+      `blocks`  d_b, the difference per block.
+    A block is `block` consecutive windows of one contig (the last block of a contig may hold fewer); neighbouring positions are
+    dependent, so the blocks have to be long against the correlation length of the data for `se` to mean anything.  Refuses tracks
+    of different shapes and fewer than two blocks."""
+    block = int(block)
+    if block < 1:
+        raise ValueError("compare_tracks: block < 1")
+    if len(track_a) != len(track_b):
+        raise ValueError(f"compare_tracks: {len(track_a)} contigs against {len(track_b)}")
+    d = []
+    for c, (ta, tb) in enumerate(zip(track_a, track_b)):
+        ta, tb = np.asarray(ta, dtype=np.float64), np.asarray(tb, dtype=np.float64)
+        if ta.ndim != 1 or ta.shape != tb.shape:
+            raise ValueError(f"compare_tracks: contig {c}: tracks of shapes {ta.shape} and {tb.shape}")
+        if len(ta):
+            d.append(np.add.reduceat(ta - tb, np.arange(0, len(ta), block)))
+    d = np.concatenate(d) if d else np.zeros(0)
+    B = len(d)
+    if B < 2:
+        raise ValueError(f"compare_tracks: {B} block(s): the jackknife needs at least two (use a smaller block)")
+    D = float(d.sum())
+    se = float(np.sqrt(B / (B - 1.0) * np.sum((d - D / B) ** 2)))
+    return {"delta": D, "se": se, "z": D / se if se > 0.0 else float(np.copysign(np.inf, D)) if D != 0.0 else 0.0, "blocks": d}
+
+
+def surprisal(track, window, lengths):
+    """-log-likelihood per base pair: per contig `-track[c] / width`, the width of a window being `window` except for the last
+    window of a contig, which is divided by its true width `lengths[c] - (n_windows - 1) window` (`lengths[c]` = the positions the
+    track of contig c covers, P_c)."""
+    window = int(window)
+    out = []
+    for c, (t, N) in enumerate(zip(track, lengths)):
+        t = np.asarray(t, dtype=np.float64)
+        N = int(N)
+        if len(t) != -(-N // window):
+            raise ValueError(f"surprisal: contig {c}: {len(t)} windows of {window} do not cover {N} positions")
+        width = np.full(len(t), float(window))
+        if len(t):
+            width[-1] = N - (len(t) - 1) * window
+        out.append(-t / width)
+    return out

@@ -27,10 +27,11 @@ def balance_hidden_states(model, M):
     return np.array(ret)
 
 
-def _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end, thinning):
-    """What `posterior` and `posterior_products` share: the hidden states, the rows handed to the manager (missing row in front,
-    `start` / `end` / `thinning` applied) and a one- or two-population manager after its `save_gamma` E-step.
-    -> `(hidden_states, obs, im)`."""
+def _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end, thinning,
+                  save_gamma=True):
+    """What `posterior`, `posterior_products` and `evidence.loglik_track` share: the hidden states, the rows handed to the manager
+    (missing row in front, `start` / `end` / `thinning` applied) and a one- or two-population manager after its E-step - a
+    `save_gamma` one unless `save_gamma=False`.  -> `(hidden_states, obs, im)`."""
     twopop = not np.isscalar(n) and len(n) == 2
     dist = model.model1 if twopop else model          # `distinguished_model` (smcpp/model.py:70-72,275-277)
     hs = balance_hidden_states(dist, M) if hidden_states is None else np.asarray(hidden_states, dtype=float)
@@ -61,7 +62,7 @@ def _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, h
     im.theta = theta
     im.rho = rho
     im.alpha = alpha
-    im.save_gamma = True
+    im.save_gamma = bool(save_gamma)
     im.E_step()
     return hs, obs, im
 
@@ -104,7 +105,7 @@ def average_coal_times(model, hidden_states):
 
 def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization_error=0.5, hidden_states=None, device=-1, a=None,
                        start=None, end=None, thinning=1, window=None, quantiles=(0.025, 0.5, 0.975), return_manager=False, transitions=False,
-                       paths=0, seed=0, grid=None, exact_windows=False):
+                       paths=0, seed=0, grid=None, exact_windows=False, loglik_windows=False):
     """What a posterior decoding is reduced to, computed on the device without ever fetching the `[M, L+1]` matrix (arguments and
     set-up as `posterior`: hidden states, the prepended missing row, `start` / `end` / `thinning`, one or two populations).
     Returns `(hidden_states, products)`; `products[c]` is a dict for contig c:
@@ -134,6 +135,9 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
       `grid_path`, `grid_mean_tmrca`, `grid_qstate`   as `path`, `mean_tmrca`, `qstate`, per grid position instead of per column.
     With `exact_windows=True` (and `window=W`) `windows` comes from `im.posterior_windows_exact`: rows that a window boundary cuts
     are walked position by position instead of being apportioned uniformly.
+    With `loglik_windows=True` (and `window=W`) each dict gains
+      `loglik_windows`   `[ceil(P / W)]`: the contig's log-likelihood per window of W positions (`im.loglik_windows`; windows as
+                         for `windows`), summing to the contig's log-likelihood.
     `return_manager=True` appends the inference manager."""
     hs, obs, im = _decode_setup(model, contigs, M, n, theta, rho, alpha, polarization_error, hidden_states, device, a, start, end,
                                 thinning)
@@ -145,6 +149,8 @@ def posterior_products(model, contigs, M, n, theta, rho, alpha=1.0, polarization
         prod = {"sites": obs[c][:, 0].copy(), "path": sm["argmax"], "mean_tmrca": sm["mean"], "qstate": sm["qstate"]}
         if window is not None:
             prod["windows"] = im.posterior_windows_exact(c, window) if exact_windows else im.posterior_windows(c, window)
+            if loglik_windows:
+                prod["loglik_windows"] = im.loglik_windows(c, window)
         if transitions:
             tr = im.posterior_transitions(c)
             prod["transitions"] = np.stack([tr["stay"], tr["up"], tr["down"]])
@@ -177,11 +183,11 @@ def save_products_npz(path, hs, products, names):
     """`.npz` of `posterior_products`: `hidden_states` and per file `<file>_sites`, `<file>_path`, `<file>_mean_tmrca`,
     `<file>_qstate` and, where they were asked for, `<file>_windows`, `<file>_transitions`, `<file>_transition_windows`,
     `<file>_path_state`, `<file>_path_up`, `<file>_path_down`, `<file>_grid_positions`, `<file>_grid_path`, `<file>_grid_mean_tmrca`,
-    `<file>_grid_qstate`."""
+    `<file>_grid_qstate`, `<file>_loglik_windows`."""
     out = {"hidden_states": hs}
     for nm, prod in zip(names, products):
         for key in ("sites", "path", "mean_tmrca", "qstate", "windows", "transitions", "transition_windows", "path_state", "path_up",
-                    "path_down", "grid_positions", "grid_path", "grid_mean_tmrca", "grid_qstate"):
+                    "path_down", "grid_positions", "grid_path", "grid_mean_tmrca", "grid_qstate", "loglik_windows"):
             if key in prod:
                 out[f"{nm}_{key}"] = prod[key]
     np.savez_compressed(path, **out)
