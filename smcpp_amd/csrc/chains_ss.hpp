@@ -71,9 +71,20 @@ struct SsArgs {
     int nk_lds = 0, key_of_slot[4] = {0, 1, 2, 3}, slot_of_key[4] = {0, 1, 2, 3};
     const double *Pinvrm = nullptr, *Prm = nullptr, *PinvT = nullptr, *PT = nullptr;   // [Ke][Mp][Mp]
     const double *dsc = nullptr;               // [Ke][Mp] scaled eigenvalues d / scale
+    // POWER JUMPS (one state per lane, no hybrid rows; round 7): inside a row of the dominant key the chains apply ONE operator
+    // A = diag(e_key) T^T `span` times without rescaling or storing, so its power A^P - formed once per E-step by k_ss_jump_tables -
+    // replaces P scan steps by one dense mat-vec on the vector held one state per lane - in the light passes and the float halo, which
+    // store nothing.  jump = P (16, 8 or 4; 0 = no jumps).
+    int jump = 0;
+    const float *jtab_f = nullptr;             // [64][64] off-diagonal part of A^P, row-major: the forward lane's row
+    const float *jtab_t = nullptr;             // [64][64] its transpose with reversed columns: the backward lane's row (lane l = state 63 - l)
+    const double *jdiag = nullptr;             // [64] diagonal of A^P
 };
 
 constexpr int SS_KE_MAX = 4;
+// rowdesc.x bit 29: a row of the jump key long enough for a jump (span - 1 >= the power in use) - marked by the host, so that
+// the kernel's test is one scalar bit test
+constexpr int SS_ROW_JUMP = 1 << 29;
 // rowdesc.x: bits 0-15 key slot, 16-23 eigen key (hybrid rows), bit 30: the row continues the caller's row of the row before it (a long
 // row of binned data cut into pieces, engine_manager.hpp: build) - the alpha stored at its START is an interior point of a row of the
 // reference's, which neither floors nor stores it: it is stored un-floored (the statistics of the next piece read it)
@@ -638,9 +649,96 @@ __device__ __forceinline__ double ss_eig_apply(const SsArgs &a, const SsEigC &c,
     return ss_eig_matvec_cold(c, m1, Mp, sx, lp, lp < 64 / c.G ? u : 0.0);
 }
 
-template <int NPL, bool ALLLDS>
+// ---- power jumps (NPL = 1): y = A^P x (forward: lane = state) / y = (A^P)^T b (backward: lane 63 - state) ----
+// No LDS: four wavefronts of a CU jumping at once would queue on the one LDS (measured: a jump through LDS tables costs what the
+// scan steps it replaces cost).  Instead every lane keeps ITS row of the table (forward: row `state` of A^P, backward: row `state`
+// of the transpose) in 64 registers, and the vector reaches the lanes through DPP: three permlane swaps leave, for q = 0..3, a
+// register X_q that holds 16-lane row q of the vector in all four rows, and v_fmac_f32_dpp with row_newbcast:n multiplies lane n of
+// that row into every lane - 64 fused instructions per product, four independent accumulators.
+// Jumps run in the LIGHT passes and in the float halo only - the walks that hand on a chunk's end vector and store nothing, so a
+// jump can change how fast the fixed point is reached, never a stored row: the stored pass and the re-run pass keep their scan steps,
+// and every row they store is bit for bit what it was.  (Tried in the stored passes too, the product in float on the off-diagonal
+// part and the diagonal term in fp64: gamma_0 then differs from the scan steps' by 1.4e-7 at M = 48, which is the distance of the
+// scan steps themselves from the restatement - a float table cannot do better, an fp64 table does not fit the registers.)
+// One power per launch: a second table would take the kernel past 168 registers, i.e. below three wavefronts per SIMD on the
+// inputs that run three.
+struct SsJumpR { float r[64]; double d; int P, sh; };      // sh = log2 P (31 without jumps: no row ever has room for one)
+template <bool BWD>
+__device__ __forceinline__ void ss_jump_load(const SsArgs &a, int lane, SsJumpR &j) {
+    j.P = a.jump;
+    j.sh = j.P == 16 ? 4 : j.P == 8 ? 3 : j.P == 4 ? 2 : 31;
+    if (!j.P) return;                                          // wave-uniform
+    const int st = BWD ? 63 - lane : lane;
+    const float4 *src = reinterpret_cast<const float4 *>((BWD ? a.jtab_t : a.jtab_f) + st * 64);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { const float4 v = src[k]; j.r[4 * k] = v.x; j.r[4 * k + 1] = v.y; j.r[4 * k + 2] = v.z; j.r[4 * k + 3] = v.w; }
+    j.d = a.jdiag[st];
+}
+#define SS_NBE_ " row_mask:0xf bank_mask:0xf\n"
+__device__ __forceinline__ float ss_jump_16(float acc, float X, const float *r) {
+    asm volatile("s_nop 1\n"
+                 "v_fmac_f32_dpp %0, %1, %2 row_newbcast:0" SS_NBE_ "v_fmac_f32_dpp %0, %1, %3 row_newbcast:1" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %4 row_newbcast:2" SS_NBE_ "v_fmac_f32_dpp %0, %1, %5 row_newbcast:3" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %6 row_newbcast:4" SS_NBE_ "v_fmac_f32_dpp %0, %1, %7 row_newbcast:5" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %8 row_newbcast:6" SS_NBE_ "v_fmac_f32_dpp %0, %1, %9 row_newbcast:7" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %10 row_newbcast:8" SS_NBE_ "v_fmac_f32_dpp %0, %1, %11 row_newbcast:9" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %12 row_newbcast:10" SS_NBE_ "v_fmac_f32_dpp %0, %1, %13 row_newbcast:11" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %14 row_newbcast:12" SS_NBE_ "v_fmac_f32_dpp %0, %1, %15 row_newbcast:13" SS_NBE_
+                 "v_fmac_f32_dpp %0, %1, %16 row_newbcast:14" SS_NBE_ "v_fmac_f32_dpp %0, %1, %17 row_newbcast:15" SS_NBE_
+                 : "+v"(acc)
+                 : "v"(X), "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]), "v"(r[8]), "v"(r[9]),
+                   "v"(r[10]), "v"(r[11]), "v"(r[12]), "v"(r[13]), "v"(r[14]), "v"(r[15]));
+    return acc;
+}
+#undef SS_NBE_
+// off-diagonal product of this lane's table row with the vector x (one entry per lane, lane order = the order of the table's columns:
+// forward lanes hold state = lane, backward lanes state = 63 - lane, and the backward table is stored with its columns reversed)
+__device__ __forceinline__ float ss_jump_mv(const SsJumpR &j, float x) {
+    const unsigned xi = __builtin_bit_cast(unsigned, x);
+    const auto s16 = __builtin_amdgcn_permlane16_swap(xi, xi, false, false);     // rows (0, 0, 2, 2) and (1, 1, 3, 3)
+    const auto sa = __builtin_amdgcn_permlane32_swap(s16[0], s16[0], false, false);     // row 0 everywhere, row 2 everywhere
+    const auto sb = __builtin_amdgcn_permlane32_swap(s16[1], s16[1], false, false);     // row 1 everywhere, row 3 everywhere
+    const float a0 = ss_jump_16(0.f, __builtin_bit_cast(float, (unsigned)sa[0]), j.r);
+    const float a1 = ss_jump_16(0.f, __builtin_bit_cast(float, (unsigned)sb[0]), j.r + 16);
+    const float a2 = ss_jump_16(0.f, __builtin_bit_cast(float, (unsigned)sa[1]), j.r + 32);
+    const float a3 = ss_jump_16(0.f, __builtin_bit_cast(float, (unsigned)sb[1]), j.r + 48);
+    return (a0 + a1) + (a2 + a3);
+}
+// the positions t .. span - 1 of a jump row that is past its first position: as many jumps as fit; returns the position the scan
+// steps continue from
+__device__ __forceinline__ int ss_jump_run(const SsJumpR &j, float &x, int t, int span) {
+    const float df = (float)j.d;
+    const int nj = (span - t) >> j.sh;
+    for (int q = 0; q < nj; ++q) x = __builtin_fmaf(df, x, ss_jump_mv(j, x));
+    return t + (nj << (j.sh & 15));
+}
+
+// The power table of the jump key (slot `slot` of E), once per E-step: wavefront i carries the unit vector of state i through P
+// steps of the chains' own fp64 forward operator (ss_fwd_step: the very arithmetic of a scan position) and ends with column i of A^P
+// - 64 independent wavefronts, P dependent steps, no squaring and no barrier.  Written as floats, row-major, for the forward lanes
+// (tf[j][i]) and transposed with reversed columns for the backward lanes, whose lane l holds state 63 - l (tt[i][63 - j]); the diagonal
+// goes to `diag` in fp64 and is zero in both tables.  grid = 16 workgroups of 4 wavefronts.
+__global__ __launch_bounds__(256) void k_ss_jump_tables(SsArgs a, int slot, float *__restrict__ tf, float *__restrict__ tt, double *__restrict__ diag) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    SsFwdC<1> cst;
+    ss_load_fwd<1>(a, lane, cst);
+    double e[1], x[1], y[1], S;
+    e[0] = a.E[(size_t)slot * 64 + lane];
+    x[0] = (lane == i && i < a.M) ? 1.0 : 0.0;
+    for (int t = 0; t < a.jump; ++t) {
+        ss_fwd_step<1>(cst, x, e, y, S);
+        x[0] = y[0];
+    }
+    const float v = lane == i ? 0.f : (float)x[0];
+    tf[lane * 64 + i] = v;
+    tt[i * 64 + (63 - lane)] = v;
+    if (lane == i) diag[i] = x[0];
+}
+
+// (JMP: the instantiation whose row loop tests for jump rows - chosen per launch, so that an input that never jumps runs the loops it had)
+template <int NPL, bool ALLLDS, bool JMP = false>
 __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double *sE, long long base, int first, int last, int lane, float (&x)[NPL]);
-template <int NPL, bool ALLLDS>
+template <int NPL, bool ALLLDS, bool JMP = false>
 __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double *sE, long long base, int rhi, int rlo, int lane, float (&b)[NPL]);
 
 template <int NPL, bool RERUN, bool HYB, bool ALLLDS, bool MIX = false, bool H32 = false>
@@ -674,7 +772,8 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
         float xf[NPL];
 #pragma unroll
         for (int k = 0; k < NPL; ++k) xf[k] = (float)x[k];
-        ss_fwd_light_rows<NPL, ALLLDS>(a, sE, ch.base, ch.h0, ch.h1, lane, xf);
+        if (NPL == 1 && !HYB && a.jump) ss_fwd_light_rows<NPL, ALLLDS, NPL == 1 && !HYB>(a, sE, ch.base, ch.h0, ch.h1, lane, xf);
+        else ss_fwd_light_rows<NPL, ALLLDS>(a, sE, ch.base, ch.h0, ch.h1, lane, xf);
 #pragma unroll
         for (int k = 0; k < NPL; ++k) x[k] = live[k] ? (double)xf[k] : 0.0;
         if (jst == 0) {
@@ -926,7 +1025,8 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
         float bf_[NPL];
 #pragma unroll
         for (int k = 0; k < NPL; ++k) bf_[k] = (float)b[k];
-        ss_bwd_light_rows<NPL, ALLLDS>(a, sE, ch.base, ch.h0, ch.h1, lane, bf_);
+        if (NPL == 1 && !HYB && a.jump) ss_bwd_light_rows<NPL, ALLLDS, NPL == 1 && !HYB>(a, sE, ch.base, ch.h0, ch.h1, lane, bf_);
+        else ss_bwd_light_rows<NPL, ALLLDS>(a, sE, ch.base, ch.h0, ch.h1, lane, bf_);
         float pt = 0.f;
 #pragma unroll
         for (int k = 0; k < NPL; ++k) pt += live[k] ? bf_[k] : 0.f;
@@ -1241,7 +1341,7 @@ __device__ __forceinline__ void ss_emission_f(const SsArgs &a, const double *sE,
 
 // float, store-free steps of the forward chain over rows first+1 .. last of the contig at `base`: x on entry = the vector at row
 // `first`, on return the (un-normalised) vector at row `last`.  The halo of a first pass (ss_forward_wave).
-template <int NPL, bool ALLLDS>
+template <int NPL, bool ALLLDS, bool JMP>
 __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double *sE, long long base, int first, int last, int lane,
                                                   float (&x)[NPL]) {
     SsLightC<NPL> cst;
@@ -1252,10 +1352,14 @@ __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double 
     ss_desc_settle(dcur); ss_desc_settle(dnxt);
     float e[NPL];
     ss_emission_f<NPL, false, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    SsJumpR jr;
+    jr.P = 0; jr.sh = 31;
+    if constexpr (JMP) ss_jump_load<false>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
         const int jl = j & 63;
         const int span = __builtin_amdgcn_readlane(dcur.y, jl);
+        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
         if (jl == 63) { dcur = dnxt; dnxt = rd[j + 65 + lane]; ss_desc_settle(dnxt); }
         const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
         float en[NPL], y[NPL], S;
@@ -1266,6 +1370,7 @@ __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double 
         for (int k = 0; k < NPL; ++k) x[k] = y[k] * inv;
         float S2;
         int t = 1;
+        if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, x[0], t, span); }
         for (; t + 1 < span; t += 2) {
             ss_fwd_step_f<NPL>(cst, x, e, y, S2);
 #pragma unroll
@@ -1284,7 +1389,7 @@ __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double 
     }
 }
 // ... and of the backward chain over rows rhi .. rlo+1 (b on entry = the vector at row rhi, on return at row rlo)
-template <int NPL, bool ALLLDS>
+template <int NPL, bool ALLLDS, bool JMP>
 __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double *sE, long long base, int rhi, int rlo, int lane,
                                                   float (&b)[NPL]) {
     SsLightC<NPL> cst;
@@ -1295,10 +1400,14 @@ __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double 
     ss_desc_settle(dcur); ss_desc_settle(dnxt);
     float e[NPL];
     ss_emission_f<NPL, true, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    SsJumpR jr;
+    jr.P = 0; jr.sh = 31;
+    if constexpr (JMP) ss_jump_load<true>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
         const int jl = j & 63;
         const int span = __builtin_amdgcn_readlane(dcur.y, jl);
+        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
         if (jl == 63) { dcur = dnxt; dnxt = rd[-(j + 65) - lane]; ss_desc_settle(dnxt); }
         const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
         float en[NPL], y[NPL], Sw;
@@ -1309,6 +1418,7 @@ __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double 
         for (int k = 0; k < NPL; ++k) b[k] = y[k] * inv;
         float S2;
         int t = 1;
+        if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, b[0], t, span); }
         for (; t + 1 < span; t += 2) {
             ss_bwd_step_f<NPL>(cst, b, e, y, S2);
 #pragma unroll
@@ -1327,7 +1437,7 @@ __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double 
     }
 }
 
-template <int NPL, bool ALLLDS, bool H32 = false>
+template <int NPL, bool ALLLDS, bool H32 = false, bool JMP = false>
 __device__ __forceinline__ void ss_forward_light(const SsArgs &a, const double *sE, int c, int lane) {
     const int M = a.M, Mp = a.Mp, pass = a.pass;
     const Chunk ch = ss_uniform_chunk(a.chunks[c]);
@@ -1351,10 +1461,14 @@ __device__ __forceinline__ void ss_forward_light(const SsArgs &a, const double *
     ss_desc_settle(dcur); ss_desc_settle(dnxt);
     float e[NPL];
     ss_emission_f<NPL, false, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    SsJumpR jr;
+    jr.P = 0; jr.sh = 31;
+    if constexpr (JMP) ss_jump_load<false>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
         const int jl = j & 63;
         const int span = __builtin_amdgcn_readlane(dcur.y, jl);
+        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
         if (jl == 63) { dcur = dnxt; dnxt = rd[j + 65 + lane]; ss_desc_settle(dnxt); }
         const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
         float en[NPL], y[NPL], S;
@@ -1367,6 +1481,7 @@ __device__ __forceinline__ void ss_forward_light(const SsArgs &a, const double *
             // two positions per trip (the DPP moves are convergent operations: the compiler will not unroll this loop itself)
             float S2;
             int t = 1;
+            if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, x[0], t, span); }
             for (; t + 1 < span; t += 2) {
                 ss_fwd_step_f<NPL, H32>(cst, x, e, y, S2);
 #pragma unroll
@@ -1392,7 +1507,7 @@ __device__ __forceinline__ void ss_forward_light(const SsArgs &a, const double *
     for (int k = 0; k < NPL; ++k) if (stor[k]) end_cur[st[k]] = live[k] ? fmaxf(x[k] * inv, ss_floor_at<NPL>(a, ch.base + ch.r1 + 1)) : 0.f;
 }
 
-template <int NPL, bool ALLLDS, bool H32 = false>
+template <int NPL, bool ALLLDS, bool H32 = false, bool JMP = false>
 __device__ __forceinline__ void ss_backward_light(const SsArgs &a, const double *sE, int c, int lane) {
     constexpr int MS = 64 * NPL;
     const int M = a.M, Mp = a.Mp, pass = a.pass;
@@ -1418,10 +1533,14 @@ __device__ __forceinline__ void ss_backward_light(const SsArgs &a, const double 
     ss_desc_settle(dcur); ss_desc_settle(dnxt);
     float e[NPL];
     ss_emission_f<NPL, true, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    SsJumpR jr;
+    jr.P = 0; jr.sh = 31;
+    if constexpr (JMP) ss_jump_load<true>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
         const int jl = j & 63;
         const int span = __builtin_amdgcn_readlane(dcur.y, jl);
+        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
         if (jl == 63) { dcur = dnxt; dnxt = rd[-(j + 65) - lane]; ss_desc_settle(dnxt); }
         const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
         float en[NPL], y[NPL], Sw;
@@ -1434,6 +1553,7 @@ __device__ __forceinline__ void ss_backward_light(const SsArgs &a, const double 
             // two positions per trip (the DPP moves are convergent operations: the compiler will not unroll this loop itself)
             float S2;
             int t = 1;
+            if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, b[0], t, span); }
             for (; t + 1 < span; t += 2) {
                 ss_bwd_step_f<NPL, H32>(cst, b, e, y, S2);
 #pragma unroll
@@ -1464,7 +1584,9 @@ __device__ __forceinline__ void ss_backward_light(const SsArgs &a, const double 
 // (the hybrid instantiation may run 8 wavefronts per workgroup - two per SIMD behind ONE copy of the eigenvector tables)
 // H32: M <= 32, one state per lane - the scans of the light passes and of the all-float stored passes skip their widest level
 template <int NPL, bool HYB, bool ALLLDS, bool H32 = false>
-__global__ __launch_bounds__(HYB ? 512 : 256) void k_chain_ss(SsArgs a) {
+// (second bound: one state per lane without hybrid rows must keep four wavefronts per SIMD - at most 128 registers - whatever the jump
+// table adds: SMCPP_SS_WPC goes up to 4)
+__global__ __launch_bounds__(HYB ? 512 : 256, (NPL == 1 && !HYB) ? 4 : 1) void k_chain_ss(SsArgs a) {
     constexpr int MS = 64 * NPL;
     extern __shared__ __attribute__((aligned(16))) double ss_lds[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1509,20 +1631,24 @@ __global__ __launch_bounds__(HYB ? 512 : 256) void k_chain_ss(SsArgs a) {
         if (NPL == 1 && !HYB && a.mixed) {
             if (a.mode_f == 0) ss_forward_wave<NPL, false, HYB, ALLLDS, true, H32>(a, ss_lds, c, lane);
             else if (a.mode_f == 1) ss_forward_wave<NPL, true, HYB, ALLLDS, true, H32>(a, ss_lds, c, lane);
+            else if (NPL == 1 && !HYB && a.jump) ss_forward_light<NPL, ALLLDS, H32, NPL == 1 && !HYB>(a, ss_lds, c, lane);
             else ss_forward_light<NPL, ALLLDS, H32>(a, ss_lds, c, lane);
         } else
         if (a.mode_f == 0) ss_forward_wave<NPL, false, HYB, ALLLDS>(a, ss_lds, c, lane);
         else if (a.mode_f == 1) ss_forward_wave<NPL, true, HYB, ALLLDS>(a, ss_lds, c, lane);
+        else if (NPL == 1 && !HYB && a.jump) ss_forward_light<NPL, ALLLDS, H32, NPL == 1 && !HYB>(a, ss_lds, c, lane);
         else ss_forward_light<NPL, ALLLDS, H32>(a, ss_lds, c, lane);
     } else {
         if (idle_b) return;
         if (NPL == 1 && !HYB && a.mixed) {
             if (a.mode_b == 0) ss_backward_wave<NPL, false, HYB, ALLLDS, true, H32>(a, ss_lds, c, lane);
             else if (a.mode_b == 1) ss_backward_wave<NPL, true, HYB, ALLLDS, true, H32>(a, ss_lds, c, lane);
+            else if (NPL == 1 && !HYB && a.jump) ss_backward_light<NPL, ALLLDS, H32, NPL == 1 && !HYB>(a, ss_lds, c, lane);
             else ss_backward_light<NPL, ALLLDS, H32>(a, ss_lds, c, lane);
         } else
         if (a.mode_b == 0) ss_backward_wave<NPL, false, HYB, ALLLDS>(a, ss_lds, c, lane);
         else if (a.mode_b == 1) ss_backward_wave<NPL, true, HYB, ALLLDS>(a, ss_lds, c, lane);
+        else if (NPL == 1 && !HYB && a.jump) ss_backward_light<NPL, ALLLDS, H32, NPL == 1 && !HYB>(a, ss_lds, c, lane);
         else ss_backward_light<NPL, ALLLDS, H32>(a, ss_lds, c, lane);
     }
 }

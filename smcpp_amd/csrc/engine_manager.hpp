@@ -163,6 +163,23 @@ struct smcpp_im {
     int ss_hyb_th = 0x7fffffff;
     static constexpr int SS_HYB_COST = 8;
     long long ss_row_cost(int span) const { return (ss_hybrid && span > ss_hyb_th) ? SS_HYB_COST : span; }
+    // Power jumps of the scan chains (chains_ss.hpp): in the history passes, every P scan steps inside a row of ONE key become one
+    // mat-vec by the P-th power of that key's operator.  pick_jump_key() decides key and power once per manager; ss_jump_P = 0: never.
+    bool ss_jump_decided = false;
+    int ss_jump_kid = -1, ss_jump_P = 0;
+    bool ss_jump_launch = false;           // the last E-step's launches jumped
+    // what pick_jump_key() charges a jump when it asks whether jumps remove 5 % of the chain work: 3 permlane swaps + 64 fused
+    // multiply-adds + 4 adds against the 25 (forward) / 38 (backward) instructions of a light-pass position.  Instruction counts,
+    // not a measurement; nothing else reads it (chunks are cut by positions).
+    static constexpr int SS_JUMP_COST = 3;
+    bool ss_jump_on() const { return ss_jump_P != 0 && ss_static && !ss_hybrid && NPL == 1; }
+    // cost of a row in scan positions with the jumps taken: the first position, the jumps, the scan steps that remain
+    long long ss_jump_cost(int span, int P) const { const long long r = span - 1; return 1 + (r / P) * SS_JUMP_COST + r % P; }
+    // (the chunk lists stay cut by POSITIONS, jumps or not: seams, halos and every count of the plan are where they were - what
+    // tests/test_gpu_seams.py places its features on)
+    void pick_jump_key();
+    DevBuf<float> d_jtab_f;                // [2][64][64] off-diagonal part of the power table and its transpose, rebuilt on every E-step
+    DevBuf<double> d_jdiag;                // [64] its diagonal
     bool ss_dirsplit = false;              // hybrid rows at M > 32: single-direction workgroups with two tables per eigen key (chains_ss.hpp)
     // eigen keys whose tables the hybrid rows keep in LDS (all of them unless they do not fit: then the most frequent ones, the
     // rest - COLD keys - read their table rows from L2; M > 32 with three or four eigen keys)
@@ -663,6 +680,44 @@ static std::vector<int> ss_chunk_counts(const std::vector<long long> &cpos, cons
     return ncs;
 }
 
+// The jump key of the scan chains and whether the input jumps at all (once per manager; chains_ss.hpp: power jumps).
+// SMCPP_SS_JUMP: 0 = never; 16, 8 or 4 = that power, whatever the size of the input (any other value: 8); unset: power 8 on inputs of
+// at least 200 000 positions.
+void smcpp_im::pick_jump_key() {
+    ss_jump_decided = true;
+    ss_jump_kid = -1; ss_jump_P = 0;
+    if (!ss_static || ss_hybrid || NPL != 1 || opt().off(smcpp_opt::O_SS_JUMP)) return;
+    int P = opt().i(smcpp_opt::O_SS_JUMP, 8);
+    if (P != 16 && P != 8 && P != 4) P = 8;
+    // positions in span > 1 rows per key, all positions
+    std::vector<long long> kpos(K, 0);
+    long long total = 0;
+    for (int c = 0; c < n_contigs; ++c)
+        for (int i = 1; i <= Ls[c]; ++i) {
+            const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+            if (ri.gid >= 0) kpos[groups[ri.gid].kid] += groups[ri.gid].span;
+            total += ri.gid < 0 ? 1 : groups[ri.gid].span;
+        }
+    int best = 0;
+    for (int k = 1; k < K; ++k)
+        if (kpos[k] > kpos[best]) best = k;
+    if (K <= 0 || kpos[best] == 0) return;
+    long long saved = 0;
+    for (int c = 0; c < n_contigs; ++c)
+        for (int i = 1; i <= Ls[c]; ++i) {
+            const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+            if (ri.gid >= 0 && groups[ri.gid].kid == best) saved += std::max<long long>(0, groups[ri.gid].span - ss_jump_cost(groups[ri.gid].span, P));
+        }
+    if (20 * saved < total) return;
+    // ... and, unless SMCPP_SS_JUMP names the power itself, on inputs of at least 200 000 positions.  Smaller inputs would gain as well
+    // (6 - 8 % of chain time on the 10 000 / 20 000-position goldens) but keep the history the existing yardsticks were set on: with a few
+    // chunks and keys of one row, the gamma sums of the float and the fp64 scans differ by 0.3 .. 2.3e-6 depending on which float
+    // history fed them (scan steps 1.3e-6, jumps by 16 / 4 / 8: 0.3 / 0.7 / 2.3e-6; either is 1.6 .. 2.1e-6 from the reference), and
+    // tests/test_gpu_parity.py holds that difference to 2e-6.  DESIGN.md section 6.
+    if (!opt().has(smcpp_opt::O_SS_JUMP) && total < 200000) return;
+    ss_jump_kid = best; ss_jump_P = P;
+}
+
 void smcpp_im::make_chunks() {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
@@ -730,6 +785,7 @@ void smcpp_im::make_chunks() {
                 }
             }
             if (ss_static) chain_mode = Mp > 64 ? 3 : 2;
+            if (!ss_jump_decided) pick_jump_key();
         }
         if (opt().i(smcpp_opt::O_COOP_BPC, 0) > 0) coop_bpc = opt().i(smcpp_opt::O_COOP_BPC, 0);
         else {
@@ -1203,6 +1259,12 @@ void smcpp_im::alloc_device() {
                 for (int c = 0; c < n_contigs; ++c)
                     for (int ell = 2; ell <= Ls[c]; ++ell)
                         if (piece_row[c][ell] == piece_row[c][ell - 1]) rd[ROWDESC_PAD + (size_t)contig_base[c] + ell].x |= SS_ROW_CONT;
+            // rows of the jump key with room for a jump behind their first position (SS_ROW_JUMP: one scalar bit test per row in the kernel)
+            if (ss_jump_P)
+                for (size_t r = 0; r < (size_t)total_rows; ++r) {
+                    const RowInfo &ri = rowinfo[r];
+                    if (ri.gid >= 0 && groups[ri.gid].kid == ss_jump_kid && groups[ri.gid].span - 1 >= ss_jump_P) rd[ROWDESC_PAD + r].x |= SS_ROW_JUMP;
+                }
             d_rowdesc_ss.upload(rd, s);
             HIPCHK(hipStreamSynchronize(s));
         }

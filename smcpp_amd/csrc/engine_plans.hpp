@@ -662,6 +662,19 @@ void smcpp_im::ss_launch_initial() {
     if (opt().has(smcpp_opt::O_DEBUG_CYCLES)) { d_dbg.alloc(16); d_dbg.zero(s); a.dbg = d_dbg.p; }
     HIPCHK(hipMemcpyAsync(d_pre, pre_stage.base, off, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(ev[EV_FIRST_PASS], s));
+    {
+        // Power jumps: the table of this E-step's operator power is built here, behind the upload above and the device-prepared
+        // emission table, in front of the first pass - 64 wavefronts x P dependent scan steps (k_ss_jump_tables)
+        ss_jump_launch = false;
+        a.jump = 0;
+        if (ss_jump_on()) {
+            ss_jump_launch = true;
+            d_jtab_f.alloc(2 * 64 * 64);
+            d_jdiag.alloc(64);
+            a.jump = ss_jump_P; a.jtab_f = d_jtab_f.p; a.jtab_t = d_jtab_f.p + 64 * 64; a.jdiag = d_jdiag.p;
+            hipLaunchKernelGGL(k_ss_jump_tables, dim3(16), dim3(256), 0, s, a, ss_slot_of_key[ss_jump_kid], d_jtab_f.p, d_jtab_f.p + 64 * 64, d_jdiag.p);
+        }
+    }
     ss_launched = ss_pass0;
     // (round 5) the passes launched up front end with the pass that is expected to rewrite no end vector - the all-skip pass behind
     // it (0.01 ms of kernel + its place in the queue) is not launched: run_chains_ss certifies from the end-vector flags

@@ -227,7 +227,7 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
                  "\"chunks_forward\": %zu, \"chunks_backward\": %zu, \"wavefronts_per_simd\": %d, \"halo_pass\": %s, "
                  "\"light_passes_forward\": %d, \"light_passes_backward\": %d, \"float_scans_in_stored_passes\": %s, "
                  "\"passes_to_certificate\": %d, \"passes_launched\": %d, \"certificate_pass_launched_up_front\": %s, "
-                 "\"save_gamma\": %s, \"eigen_free_statistics\": %s, \"per_row_gamma\": \"%s\", \"long_rows_cut\": %s, \"warm_start\": %s, \"host_threads\": %d}",
+                 "\"save_gamma\": %s, \"eigen_free_statistics\": %s, \"per_row_gamma\": \"%s\", \"long_rows_cut\": %s, \"warm_start\": %s, \"host_threads\": %d",
                  fam, im->ss_static ? "true" : "false", im->ss_hybrid ? "true" : "false", im->M, im->Mp, im->NPL, im->K, im->Ke,
                  (long long)(im->total_rows - im->n_contigs), (long long)im->ss_positions, im->ss_max_span, im->chunks.size(),
                  im->chunks_b.size(), im->ss_wpc, (im->ss_static && im->ss_args.halo) ? "true" : "false", im->ss_light_f, im->ss_light_b,
@@ -236,6 +236,15 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
                  im->eigfree ? "true" : "false", !im->save_gamma ? "none" : im->eigfree ? "scan steps" : im->stats_plan.gamma_form == StatsPlan::GAMMA_PIECES ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
                  im->warm_start ? "true" : "false", omp_get_max_threads());
         s += t;
+        {
+            // power jumps of the scan chains: `eligible` is the manager's decision (input, state count, SMCPP_SS_JUMP), `run` whether the
+            // last E-step's launches jumped; key = index into the caller's key list, -1 = none
+            const bool el = im->ss_jump_on();
+            snprintf(t, sizeof t, ", \"power_jumps\": {\"eligible\": %s, \"run\": %s, \"key\": %d, \"key_slot\": %d, \"powers\": [%s]}}",
+                     el ? "true" : "false", im->ss_jump_launch ? "true" : "false", el ? im->ss_jump_kid : -1,
+                     el && !im->ss_slot_of_key.empty() ? im->ss_slot_of_key[im->ss_jump_kid] : -1, el ? std::to_string(im->ss_jump_P).c_str() : "");
+            s += t;
+        }
         // the statistics plan of the last E-step (null before the first one): the stream of every branch, the form of every kernel family
         const StatsPlan &p = im->stats_plan;
         static const char *const stream[] = {"main", "second", "third", "high priority"}, *const rank[] = {"per slab", "teams", "wide"};
