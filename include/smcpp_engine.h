@@ -472,6 +472,45 @@ int smcpp_loglik_positions(smcpp_im *im, int contig, long long pos0, long long p
 int smcpp_loglik_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
                          double *out /* [n_windows]; NULL: only n_windows */);
 
+/* ---- score track (score_track_dev.hpp): WHERE along contig c the derivative of the log-likelihood with respect to the model comes
+ * from.  The reference knows that derivative only as one vector per manager, the Jacobian of InferenceManager::Q
+ * (src/inference_manager.cpp:116-126; at the E-step's own parameters it is the gradient of the log-likelihood, by Fisher's
+ * identity); the two entries split it along the contig.  All values are the arrays the getters return, floors included (a floored
+ * entry has a zero Jacobian): with nder >= 1 directions from the last smcpp_set_params / _twopop, elementwise
+ *     G_pi,d = dpi_d / pi,     G_T,d = dT_d / T,     G_E,d[k] = dE_d[k] / E[k].
+ * Conventions as for smcpp_posterior_transitions: for position p of row l, with key k_l,
+ *     xi_p(i, j) = x_{p-1}(i) T(i, j) e(j) y_p(j) / Z_p,     gamma_p(j) = sum_i xi_p(i, j),
+ *     u_p[d] = sum_ij xi_p(i, j) G_T,d(i, j)            (transition part)
+ *            + sum_j gamma_p(j) G_E,d[k_l](j)            (emission part),
+ *     u_0[d] = sum_m gamma_0(m) G_pi,d(m)                (initial part, position 0 only),
+ * and score_rows[d, l] = sum_{p in row l} u_p[d]; column 0 holds u_0.  gamma_0 is the NORMALISED column 0 (column 0 of
+ * smcpp_posterior_columns(normalize = 1)), so that the sum of a contig's columns is the gradient of its log-likelihood.  Summed
+ * over a contig's columns and over contigs the emission part is rows 1 + 2 and the transition part row 3 of smcpp_q's Jacobian on
+ * the same E-step; row 0 of that Jacobian is sum_c m_c u_0,c with m_c the mass of contig c's column 0 AS STORED - the reference's
+ * gamma[:, 0] = alpha_0 o beta_0 with beta_0 / sum beta_0 (src/hmm.cpp:150), which Q weighs log pi with and which does not sum to one.
+ * x and y are those of the transition products: the stored float alpha at the row's start, the stored beta at its end, the O(M)
+ * scan steps in between; where the plan cut long rows the pieces of a caller's row are added up on the device in ascending order.
+ * A value is a pure function of the stored vectors, the tables and the row: not of the selection, the launch shape
+ * (SMCPP_SCORE_WAVES), the call order or what ran before; the posterior buffers, the statistics and the loglik track are neither
+ * needed beyond the stored vectors nor disturbed.  The Jacobian of a device-prepared emission table is copied out without
+ * replacing the host's table, so a later smcpp_q KEEPS its device route after a score call ("q_route" stays what it was).
+ * smcpp_describe reports "score_items" (engine rows walked), "score_waves" and "score_park" ("lds": where a block's vectors wait).
+ * Each call fails before anything is launched, and leaves the manager usable, when no E-step has run, the last one ran without
+ * save_gamma, the contig index is out of range, the parameters were set again since the last E-step, they carry no derivative
+ * seeds (nder = 0, or smcpp_set_raw), the transition matrix lacks the semiseparable structure, there are more than 64 hidden states
+ * (the kernel keeps one column of the M x M accumulator per lane), the selection is bad (start < 0, stop > L + 1, start >= stop,
+ * step < 1) or window_bp < 1, an output would exceed 2^31 - 1 elements or the scratch 1 GiB.
+ *
+ * smcpp_score_rows: the column selection range(start, stop, step) over 0 .. L, the selection rule of smcpp_posterior_summary.
+ * parts != 0: the three parts; parts == 0: their sum (initial + emission) + transition, in that order. */
+int smcpp_score_rows(smcpp_im *im, int contig, long long start, long long stop, long long step, int parts,
+                     double *out /* parts == 0: [nder x ncols]; parts != 0: [3 x nder x ncols] initial, emission, transition; NULL: the checks alone */);
+/* smcpp_score_windows: per window of window_bp base pairs (windows as in smcpp_posterior_transition_windows), a row apportioned
+ * uniformly over its base pairs: out[d, w] = sum_l overlap(l, w) / s_l * score_rows[d, l], rows added in ascending order; column 0's
+ * initial part goes to window 0, in front of the rows.  *n_windows = ceil(P_L / W). */
+int smcpp_score_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
+                        double *out /* [nder x n_windows] row-major; NULL: only n_windows */);
+
 /* ---- simulation (simulate_dev.hpp): draws of (hidden path, observations) from the model the manager holds - the process whose
  * marginal likelihood the E-step computes.  A simulated contig has positions 1 .. N; position 0 is column 0 and carries no
  * observation:

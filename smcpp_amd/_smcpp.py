@@ -338,6 +338,31 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_loglik_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
         return out
 
+    def score_rows(self, c=0, start=0, stop=None, step=1, parts=False):
+        """`[nder, ncols]`: d loglik / d direction contributed by the caller's rows `range(start, stop, step)` of contig `c` under the
+        last `save_gamma` E-step, for the `nder` derivative seeds of the parameters it ran on (a differentiable model); column 0
+        holds the initial distribution's share.  `parts=True`: `[3, nder, ncols]`, the initial, emission and transition part; the
+        last two sum over all columns and contigs to rows 1 + 2 and 3 of `Q_with_gradient()`'s Jacobian (row 0 weighs the initial
+        part by the stored, unnormalised mass of column 0).  At most 64 hidden states.
+        (include/smcpp_engine.h: smcpp_score_rows.)"""
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        parts = 1 if parts else 0
+        E.check(E.lib().smcpp_score_rows(self._im, int(c), start, stop, step, parts, None))        # (the checks alone)
+        nder = E.lib().smcpp_num_derivatives(self._im)
+        out = np.empty((3, nder, ncols) if parts else (nder, ncols))
+        E.check(E.lib().smcpp_score_rows(self._im, int(c), start, stop, step, parts, E.dptr(out)))
+        return out
+
+    def score_windows(self, c=0, window=10_000):
+        """`[nder, ceil(P_L / window)]`: the score of contig `c` per window of `window` base pairs, every row apportioned uniformly
+        over its base pairs (windows as in `posterior_transition_windows`); column 0's share goes to window 0, and the windows sum
+        to `score_rows(c).sum(1)`.  (include/smcpp_engine.h: smcpp_score_windows.)"""
+        nw = C.c_longlong(0)
+        E.check(E.lib().smcpp_score_windows(self._im, int(c), int(window), C.byref(nw), None))
+        out = np.empty((E.lib().smcpp_num_derivatives(self._im), nw.value))
+        E.check(E.lib().smcpp_score_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
+        return out
+
     def _hmm_tables(self):
         """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""
         K = E.lib().smcpp_num_keys(self._im)

@@ -119,6 +119,8 @@ cdef extern from "smcpp_engine.h":
     int smcpp_loglik_rows(smcpp_im *im, int contig, long long start, long long stop, long long step, double *out) nogil
     int smcpp_loglik_positions(smcpp_im *im, int contig, long long pos0, long long pos1, long long step, double *out) nogil
     int smcpp_loglik_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
+    int smcpp_score_rows(smcpp_im *im, int contig, long long start, long long stop, long long step, int parts, double *out) nogil
+    int smcpp_score_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
     int smcpp_simulate(smcpp_im *im, int n_contigs, const long long *lengths, int n_alpha, const int *alpha_keys, int quiet, unsigned long long seed, long long contig0, long long rep0, long long nreps, long long cap, const long long *resume_in, int *x0, long long *n_events, long long *pos, int *state, int *key, long long *resume_out) nogil
 # --- end generated ---
 
@@ -601,6 +603,38 @@ cdef class _PyInferenceManager:
             rc = smcpp_loglik_windows(self._im, cc, W, &nw, op)
         _check(rc)
         return out[:nw] if nw < out.shape[0] else out
+
+    def score_rows(self, c=0, start=0, stop=None, step=1, parts=False):
+        """`[nder, ncols]` (`parts=True`: `[3, nder, ncols]`, the initial, emission and transition part): d loglik / d direction
+        contributed by the caller's rows `range(start, stop, step)` of contig `c` under the last `save_gamma` E-step of a
+        differentiable model; column 0 holds the initial distribution's share.  (include/smcpp_engine.h: smcpp_score_rows.)"""
+        start, stop, step, ncols = self._selection(c, start, stop, step)
+        cdef int cc = c, rc, pt = 1 if parts else 0
+        cdef long long a = start, b = stop, st = step
+        with nogil:
+            rc = smcpp_score_rows(self._im, cc, a, b, st, pt, NULL)                                  # (the checks alone)
+        _check(rc)
+        cdef int nder = smcpp_num_derivatives(self._im)
+        cdef np.ndarray[double, ndim=1] out = np.empty(max((3 if pt else 1) * nder * ncols, 1))
+        cdef double *op = &out[0]
+        with nogil:
+            rc = smcpp_score_rows(self._im, cc, a, b, st, pt, op)
+        _check(rc)
+        return out[:3 * nder * ncols].reshape(3, nder, ncols) if pt else out[:nder * ncols].reshape(nder, ncols)
+
+    def score_windows(self, c=0, window=10_000):
+        """`[nder, ceil(P_L / window)]`: the score of contig `c` per window of `window` base pairs, every row apportioned uniformly
+        over its base pairs; column 0's share goes to window 0.  (include/smcpp_engine.h: smcpp_score_windows.)"""
+        cdef int cc = c, rc
+        cdef long long W = window, nw = 0
+        _check(smcpp_score_windows(self._im, cc, W, &nw, NULL))
+        cdef int nder = smcpp_num_derivatives(self._im)
+        cdef np.ndarray[double, ndim=1] out = np.empty(max(nder * nw, 1))
+        cdef double *op = &out[0]
+        with nogil:
+            rc = smcpp_score_windows(self._im, cc, W, &nw, op)
+        _check(rc)
+        return out[:nder * nw].reshape(nder, nw)
 
     def _hmm_tables(self):
         """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""

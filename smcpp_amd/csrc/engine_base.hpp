@@ -347,7 +347,8 @@ struct DevPrep {
     }
     const int *flags() const { return emulate ? e_flags : h_flags; }
     // Results to the host (after the stream has drained): E [Kk][M], dE [Kk*M][nder], sfs [M][C], dsfs [M*C][nder]
-    void fetch(std::vector<double> &Ev, std::vector<double> &dEv, std::vector<double> &sfs, std::vector<double> &dsfs) {
+    // (with_sfs = false: the emission table and its Jacobian alone; sfs / dsfs are left as they are)
+    void fetch(std::vector<double> &Ev, std::vector<double> &dEv, std::vector<double> &sfs, std::vector<double> &dsfs, bool with_sfs = true) {
         const int C = 3 * (n + 1), nder = last_nder;
         std::vector<double> pl;
         auto get = [&](const DevBuf<double> &d, const std::vector<double> &e, size_t cnt, std::vector<double> &out) {
@@ -356,13 +357,14 @@ struct DevPrep {
             else HIPCHK(hipMemcpy(out.data(), d.p, cnt * sizeof(double), hipMemcpyDeviceToHost));
         };
         get(d_Eg_v, e_Eg_v, (size_t)Kk * M, Ev);
-        get(d_sfs_v, e_sfs_v, (size_t)M * C, sfs);
-        dEv.clear(); dsfs.clear();
+        if (with_sfs) { get(d_sfs_v, e_sfs_v, (size_t)M * C, sfs); dsfs.clear(); }
+        dEv.clear();
         if (nder) {
             get(d_Eg_d, e_Eg_d, (size_t)nder * Kk * M, pl);
             dEv.resize(pl.size());
             const size_t sz = (size_t)Kk * M;
             for (int d = 0; d < nder; ++d) for (size_t i = 0; i < sz; ++i) dEv[i * nder + d] = pl[(size_t)d * sz + i];
+            if (!with_sfs) return;
             get(d_sfs_d, e_sfs_d, (size_t)nder * M * C, pl);
             dsfs.resize(pl.size());
             const size_t s2 = (size_t)M * C;

@@ -1270,6 +1270,175 @@ int smcpp_loglik_windows(smcpp_im *im, int c, long long window_bp, long long *n_
     API_END
 }
 
+// ---- score track (score_track_dev.hpp) ----
+// Everything a score call needs besides its own arguments; -> the checkpoint vectors a wavefront needs on contig c.
+int smcpp_im::score_check(int c) {
+    if (!estep_done) throw std::runtime_error("score track: no E-step has been run on this manager yet");
+    if (!gamma_valid) throw std::runtime_error("score track: save_gamma was not set for the last E-step");
+    if (c < 0 || c >= n_contigs) throw std::runtime_error("contig index out of range");
+    if (dirty)
+        throw std::runtime_error("score track: the parameters were set again after the last E-step, whose stored vectors belong to the "
+                                 "earlier ones: run the E-step again");
+    // the walk is the transition products': the same structure of T (what an arbitrary smcpp_set_raw matrix lacks), the same generators
+    try { post_transitions_check(); }
+    catch (const std::runtime_error &e) { throw std::runtime_error(std::string("score track: ") + e.what()); }
+    if (have_raw)
+        throw std::runtime_error("score track: the parameters were set with smcpp_set_raw: no model, no derivative seeds");
+    if (nder < 1)
+        throw std::runtime_error("score track: the parameters carry no derivative seeds (nder = 0): set them with seeds and run the "
+                                 "E-step again");
+    if (M > 64 || NPL != 1)
+        throw std::runtime_error("score track: more than 64 hidden states (" + std::to_string(M) + "): the kernel keeps one column of the "
+                                 "M x M accumulator per lane and exists at one state per lane only");
+    int smax = 1;                                     // the contig's longest engine row
+    for (int i = 1; i <= Ls[c]; ++i) {
+        const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+        if (ri.gid >= 0) smax = std::max(smax, groups[ri.gid].span);
+    }
+    const int nck = (smax + SC_BLK - 1) / SC_BLK - 1;
+    // scratch: the three parts of every direction per engine row + one wavefront's checkpoints at the least
+    const size_t bytes = ((size_t)3 * nder * ((size_t)Ls[c] + 1) + (size_t)nck * 64) * sizeof(double);
+    if (bytes > (1ull << 30))
+        throw std::runtime_error("score track: the scratch (" + std::to_string(nder) + " directions x 3 parts x " + std::to_string(Ls[c] + 1) +
+                                 " engine rows, the checkpoints of a row of " + std::to_string(smax) + " positions) exceeds the cap of 1 GiB");
+    return nck;
+}
+
+static void score_cap(long long per_col, long long ncols, const char *what) {
+    if (ncols > ((1LL << 31) - 1) / std::max<long long>(1, per_col))
+        throw std::runtime_error(std::string("score track: ") + what + " (" + std::to_string(per_col) + " x " + std::to_string(ncols) +
+                                 ") exceed the cap of 2^31 - 1 elements per call: ask for a narrower selection or a wider window");
+}
+
+// G_pi [nder][64] | dT [nder][64][64] | G_E [K][nder][64] from the host arrays the Jacobian getters copy out, zero beyond M and
+// where a value is not positive.  A device-prepared emission table is FETCHED into locals: E_on_dev stays as it is.
+void smcpp_im::score_tables() {
+    if (sc_tab_valid) return;
+    HIPCHK(hipSetDevice(device));
+    prepare_params();                                  // (fresh since the E-step: !dirty)
+    ensure_dT();
+    std::vector<double> Eloc, dEloc;
+    const std::vector<double> *Ev = &E, *dEv = &dE;
+    if (E_on_dev) {
+        HIPCHK(hipStreamSynchronize(stream));
+        std::vector<double> Ep, dEp, em, dem;
+        dprep->fetch(Ep, dEp, em, dem, false);           // (the table and its Jacobian alone)
+        dprep->check_flags();
+        if (!have_global) { Eloc.swap(Ep); dEloc.swap(dEp); }
+        else {
+            Eloc.assign((size_t)K * M, 0.0);
+            dEloc.assign((size_t)K * M * nder, 0.0);
+            for (int k = 0; k < K; ++k) {
+                const int kg = local_to_global[k];
+                std::memcpy(&Eloc[(size_t)k * M], &Ep[(size_t)kg * M], sizeof(double) * M);
+                std::memcpy(&dEloc[(size_t)k * M * nder], &dEp[(size_t)kg * M * nder], sizeof(double) * M * nder);
+            }
+        }
+        Ev = &Eloc; dEv = &dEloc;
+    }
+    const size_t nd = (size_t)nder;
+    if (dpi.size() != (size_t)M * nd || dT.size() != (size_t)M * M * nd || Ev->size() != (size_t)K * M || dEv->size() != (size_t)K * M * nd)
+        throw std::runtime_error("score track: the Jacobians of pi, T and E are not available for the last E-step's parameters");
+    std::vector<double> tab(nd * 64 + nd * 64 * 64 + (size_t)K * nd * 64, 0.0);
+    double *gp = tab.data(), *gt = gp + nd * 64, *ge = gt + nd * 64 * 64;
+    for (int d = 0; d < nder; ++d) {
+        for (int i = 0; i < M; ++i) gp[d * 64 + i] = pi[i] > 0.0 ? dpi[(size_t)i * nd + d] / pi[i] : 0.0;
+        for (int i = 0; i < M; ++i)
+            for (int j = 0; j < M; ++j) gt[((size_t)d * 64 + i) * 64 + j] = dT[((size_t)i * M + j) * nd + d];
+        for (int k = 0; k < K; ++k)
+            for (int i = 0; i < M; ++i) {
+                const double e = (*Ev)[(size_t)k * M + i];
+                ge[((size_t)k * nd + d) * 64 + i] = e > 0.0 ? (*dEv)[((size_t)k * M + i) * nd + d] / e : 0.0;
+            }
+    }
+    d_sc_tab.upload(tab, stream);
+    HIPCHK(hipStreamSynchronize(stream));              // (`tab` is a local: the copy has to be done before it goes)
+    sc_tab_valid = true;
+}
+
+// The parts (parts != 0: [3][nder][ncols]) or the total ([nder][ncols]) of caller's rows start, start + step, .. of contig c, on the
+// device, on `stream`.  The arguments have been checked (score_check -> nck, the caps).
+const double *smcpp_im::score_rows(int c, long long start, long long step, long long ncols, int parts, int nck) {
+    HIPCHK(hipSetDevice(device));
+    score_tables();
+    const int Le = Ls[c];
+    const int *first = piece_first_dev(c);
+    d_pt_gen.upload(ss_gen, stream);                   // (the transition products' copy of the generators; ss_gen is a member: it outlives the copy)
+    SsArgs sa = SsArgs();
+    sa.M = M; sa.Mp = Mp;
+    const double *gd = d_pt_gen.p;
+    sa.f_dc = gd; sa.f_g = gd + 64; sa.f_cg = gd + 2 * 64; sa.f_b = gd + 3 * 64; sa.f_a = gd + 4 * 64; sa.f_d = gd + 5 * 64;
+    sa.b_dc = gd + 6 * 64; sa.b_g = gd + 7 * 64; sa.b_b = gd + 8 * 64; sa.b_a = gd + 9 * 64;
+    sa.c0 = ss_c0;
+    ScArgs a = ScArgs();
+    a.M = M; a.Mp = Mp; a.L = Le; a.nck = nck; a.nder = nder; a.base = contig_base[c];
+    // one wavefront per engine row, persistent: a workgroup's parked vectors fill a CU's LDS, so 4 wavefronts per CU are resident;
+    // fewer where SMCPP_SCORE_WAVES says so or the checkpoints of a very long row would pass 1 GiB with the parts
+    long long nw = std::max<long long>(1, std::min<long long>(Le, 1024));      // (a contig without rows: wavefront 0 writes column 0)
+    if (opt().has(smcpp_opt::O_SCORE_WAVES)) nw = std::min(nw, std::max<long long>(1, opt().ll(smcpp_opt::O_SCORE_WAVES, 1)));
+    if (nck > 0) {
+        const size_t left = (1ull << 30) - (size_t)3 * nder * ((size_t)Le + 1) * sizeof(double);
+        nw = std::max<long long>(1, std::min<long long>(nw, (long long)(left / ((size_t)nck * 64 * sizeof(double)))));
+    }
+    d_sc_ckpt.alloc(std::max<size_t>(1, (size_t)nw * nck * 64));
+    d_sc_eng.alloc((size_t)3 * nder * ((size_t)Le + 1));
+    a.rowinfo = d_rowinfo.p; a.g_span = d_g_span.p; a.E = d_E.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
+    a.gamma0 = d_gamma0.p + (size_t)c * Mp;
+    a.Gpi = d_sc_tab.p; a.dT = a.Gpi + (size_t)nder * 64; a.GE = a.dT + (size_t)nder * 64 * 64;
+    a.ckpt = d_sc_ckpt.p; a.out = d_sc_eng.p;
+    sc_waves = (int)nw; sc_items = Le;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_score_rows), hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_BYTES));
+    hipLaunchKernelGGL(k_score_rows, dim3((unsigned)ceil_div(nw, 4)), dim3(256), SC_LDS_BYTES, stream, sa, a, (int)nw);
+    HIPCHK(hipGetLastError());
+    PostSel sel;
+    sel.start = start; sel.step = step; sel.ncols = ncols;
+    d_sc_sel.alloc((size_t)(parts ? 3 : 1) * nder * ncols);
+    hipLaunchKernelGGL(k_score_select, dim3((unsigned)ceil_div(ncols * nder, 256)), dim3(256), 0, stream, sel, (long long)Le, nder, parts,
+                       first, (const double *)d_sc_eng.p, d_sc_sel.p);
+    HIPCHK(hipGetLastError());
+    return d_sc_sel.p;
+}
+
+int smcpp_score_rows(smcpp_im *im, int c, long long start, long long stop, long long step, int parts, double *out) {
+    API_BEGIN
+    const int nck = im->score_check(c);
+    const long long ncols = post_check_selection(im, c, start, stop, step);
+    score_cap((parts ? 3LL : 1LL) * im->nder, ncols, "the outputs");
+    if (!out) return 0;
+    const double *d = im->score_rows(c, start, step, ncols, parts, nck);
+    HIPCHK(hipMemcpyAsync(out, d, sizeof(double) * (size_t)(parts ? 3 : 1) * im->nder * ncols, hipMemcpyDeviceToHost, im->stream));
+    HIPCHK(hipStreamSynchronize(im->stream));
+    API_END
+}
+
+int smcpp_score_windows(smcpp_im *im, int c, long long window_bp, long long *n_windows, double *out) {
+    API_BEGIN
+    const int nck = im->score_check(c);
+    if (window_bp < 1) throw std::runtime_error("score track: window_bp < 1");
+    const std::vector<long long> &P = im->user_prefix[c];
+    const long long L = im->user_Ls[c];
+    const long long nwin = (P[L] + window_bp - 1) / window_bp;
+    if (n_windows) *n_windows = nwin;
+    score_cap(im->nder, nwin, "the windows");
+    if (!out) return 0;
+    const double *v = im->score_rows(c, 0, 1, L + 1, 0, nck);
+    hipStream_t s = im->stream;
+    if (im->d_user_prefix.size() != (size_t)im->n_contigs) im->d_user_prefix.resize(im->n_contigs);
+    if (!im->d_user_prefix[c].p) {
+        im->d_user_prefix[c].upload(P, s);             // (P is a member: it outlives the copy)
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    if (nwin > 0) {                                    // (a contig without rows has no base pairs and no windows)
+        im->d_sc_out.alloc((size_t)im->nder * nwin);
+        hipLaunchKernelGGL(k_score_windows, dim3((unsigned)ceil_div(nwin, 4)), dim3(256), 0, s, L, window_bp, nwin, im->nder,
+                           (const long long *)im->d_user_prefix[c].p, v, im->d_sc_out.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, im->d_sc_out.p, sizeof(double) * (size_t)im->nder * nwin, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
 int smcpp_gamma_cols(smcpp_im *im, int c) {
     if (c < 0 || c >= im->n_contigs) return -1;
     return im->gamma_valid ? im->user_Ls[c] + 1 : 1;

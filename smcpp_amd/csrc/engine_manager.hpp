@@ -284,6 +284,17 @@ struct smcpp_im {
     const double *ll_prefix(int c);               // pre [Le + 1] on the device, on `stream`
     void ll_table(int c, long long pos0, long long pos1, long long step, bool windows);   // -> ll_items, ll_nslots (host)
     void ll_walk(int c, long long step, double *slots);                                   // k_ll_walk over ll_items (not empty)
+    // score track (score_track_dev.hpp, smcpp_score_rows / _windows): buffers of its own - the posterior products' and the loglik
+    // track's are neither read nor written.  The tables G_pi | dT | G_E of the last E-step's parameters (built from the host Jacobians
+    // on the first call behind an E-step), the checkpoints of long rows, the parts per engine row, per selected caller's row, the
+    // windows (the generators travel in the transition products' d_pt_gen: constants of the E-step, uploaded by every walking call)
+    DevBuf<double> d_sc_tab, d_sc_ckpt, d_sc_eng, d_sc_sel, d_sc_out;
+    bool sc_tab_valid = false;                    // d_sc_tab belongs to the last E-step (cleared by estep())
+    int sc_waves = 0;                             // wavefronts of the last score call (smcpp_describe)
+    long long sc_items = 0;                       // engine rows it walked
+    int score_check(int c);                       // throws unless a score call can run on contig c; -> checkpoint vectors per wavefront
+    void score_tables();                          // -> d_sc_tab (keeps E_on_dev: a later smcpp_q stays on its device route)
+    const double *score_rows(int c, long long start, long long step, long long ncols, int parts, int nck);   // -> device, on `stream`
     // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
     std::vector<GPiece> gp_pieces;
     std::vector<GTile> gp_tiles;

@@ -275,6 +275,9 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // from the stored float vector moved the row's evidence at worst, |A_span / log c_r - 1|
         snprintf(t, sizeof t, ", \"ll_items\": %lld, \"ll_waves\": %d, \"ll_walk_worst_ratio\": %.6g", im->ll_nitems, im->ll_waves, im->ll_worst);
         s += t;
+        // ... and of the last score track call: the engine rows it walked, its wavefronts and where a block's vectors are parked
+        s += ", \"score_items\": " + std::to_string(im->sc_items) + ", \"score_waves\": " + std::to_string(im->sc_waves);
+        s += ", \"score_park\": \"lds\"";
     }
     s += "}";
     if (buf && cap > 0) {

@@ -1,0 +1,116 @@
+"""What the score track costs beside the `save_gamma` E-step and the posterior transition products of the same run.
+
+Two inputs, one manager each, in one process, the model differentiable in every piece (16 directions):
+
+  binned100M_M64  the binned 100 Mbp contig at M = 64, n = 20 (rows of 100 bp bins): short rows, the per-row contraction dominates
+  posterior64     the input of `bench.py --workload posterior64` cut to --rows rows: M = 64, n = 8, un-binned
+                  (`synth_posterior_contig`): rows of up to 10^5 positions, the walk dominates
+
+Per input: two `save_gamma` E-steps to settle, then `--repeats` rounds after `--warmup` of (a) the E-step (with its 16-direction
+preparation), wall clock up to the log-likelihood on the host, (b) `posterior_transitions(0)`, (c) `score_rows(0)`,
+(d) `score_rows(0, parts=True)`, (e) `score_windows(0, W)`; every call ends in a device synchronise and a copy to the host.  The first
+score call behind an E-step also builds and uploads the tables (G_pi, dT, G_E); it is timed apart as `score_first_call_ms`.  Reported
+per leg: the minimum, the median and the spread (max - min); the launch shape (`score_items`, `score_waves`, `score_park`; read once,
+outside the timed rounds), the ratios (c) / (b) and (c) / (a), and how far the score's sum lies from Q's gradient.
+One JSON line per input, to stdout and appended to --out.
+
+    python tools/score_track_probe.py [--rows N] [--repeats K] [--warmup W] [--window BP] [--only NAME] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=10_000, help="rows of the posterior64 input")
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--window", type=int, default=10_000)
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "score_track.log"))
+    args = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    from smcpp_amd import _smcpp, synth
+    from smcpp_amd.model import PiecewiseModel
+
+    a, s_ = synth.model_pieces()
+
+    def posterior64():
+        return 64, 8, synth.synth_posterior_contig(args.rows, 8, seed=7), 2e-4, 6e-5
+
+    def binned():
+        return 64, 20, np.ascontiguousarray(synth.synth_contig(0, 100_000_000, 20), dtype=np.int32), synth.THETA, synth.RHO
+
+    inputs = {"binned100M_M64": binned, "posterior64": posterior64}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        if not args.only:                  # (a run of one input appends its line)
+            open(args.out, "w").close()
+    for name, make in inputs.items():
+        if args.only and name != args.only:
+            continue
+        M, n, contig, theta, rho = make()
+        im = _smcpp.PyOnePopInferenceManager(n, [contig], synth.hidden_states(M), ("pop1",), 0.5, device=0)
+        model = PiecewiseModel(a, s_, 1e4, pid="pop1")
+        model.differentiable = True
+        im.model = model
+        im.theta = theta; im.rho = rho; im.alpha = 1.0
+        im.save_gamma = True
+        im.E_step()
+        im.E_step()
+        im.loglik()
+        t0 = time.perf_counter()
+        im.score_rows(0)
+        first = 1e3 * (time.perf_counter() - t0)
+
+        legs = {"estep_save_gamma": None, "posterior_transitions": lambda: im.posterior_transitions(0),
+                "score_rows": lambda: im.score_rows(0), "score_rows_parts": lambda: im.score_rows(0, parts=True),
+                "score_windows": lambda: im.score_windows(0, args.window)}
+        times = {k: [] for k in legs}
+        for r in range(args.warmup + args.repeats):
+            for k, f in legs.items():
+                t0 = time.perf_counter()
+                if f is None:
+                    im.E_step()
+                    im.loglik()
+                else:
+                    f()
+                dt = 1e3 * (time.perf_counter() - t0)
+                if f is None:
+                    im.score_rows(0, 0, 1)  # (the tables of this E-step: built here, outside the score legs)
+                if r >= args.warmup:
+                    times[k].append(dt)
+        rows = im.score_rows(0, parts=True)
+        _, jac = im.Q_with_gradient()
+        d = im.describe()                   # (the launch shape of the last score call; the route of the Q behind it)
+        m0 = float(im.posterior_columns(0, 0, 1, normalize=False).sum())       # (Q weighs log pi with the stored, unnormalised column 0)
+        want = np.stack([jac[0] / m0, jac[1] + jac[2], jac[3]])
+        off = float(np.max(np.abs(rows.sum(axis=2) - want) / np.maximum(np.abs(rows).sum(axis=2), 1e-300)))
+        plan = d["plan"]
+        best = {k: min(v) for k, v in times.items()}
+        res = {"input": name, "M": M, "directions": int(rows.shape[1]), "rows": len(contig), "positions": int(contig[:, 0].astype(np.int64).sum()),
+               "longest_row": int(contig[:, 0].max()), "window": args.window, "repeats": args.repeats,
+               "plan": {k: plan[k] for k in ("chain_family", "states_per_lane", "long_rows_cut", "hybrid_rows")},
+               "launch": {"score_items": d["score_items"], "score_waves": d["score_waves"], "score_park": d["score_park"]},
+               "q_route": d["q_route"], "score_first_call_ms": round(first, 3),
+               "score_rows_over_posterior_transitions": round(best["score_rows"] / best["posterior_transitions"], 3),
+               "score_rows_over_estep": round(best["score_rows"] / best["estep_save_gamma"], 3),
+               "parts_sum_off_q_jacobian_rel": off,
+               "legs": {k: {"min_ms": round(min(v), 3), "median_ms": round(float(np.median(v)), 3), "spread_ms": round(max(v) - min(v), 3)}
+                        for k, v in times.items()}}
+        line = json.dumps(res)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+        del im
+
+
+if __name__ == "__main__":
+    main()
