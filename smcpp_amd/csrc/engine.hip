@@ -46,12 +46,13 @@
 #include "loglik_track_dev.hpp"      // log-likelihood track: log c per caller's row, l(p) on a grid of positions, per window
 #include "simulate_dev.hpp"          // simulation: (hidden path, observations) drawn from the model, event by event
 
-// The engine is one translation unit in seven parts (each part sees everything above it):
+// The engine is one translation unit in eight parts (each part sees everything above it):
 #include "engine_base.hpp"        // logging, pinned arena, device buffers, the device route of the cold preparation (DevPrep, TwoPopDevCsfs)
 #include "engine_manager.hpp"     // the manager (struct smcpp_im): observation layout, chunks, slabs, device allocation
 #include "engine_params.hpp"      // parameters: cold preparation (host and device routes), device Q / gradient, uploads
 #include "engine_plans.hpp"       // launch plans: chain families, the scan chains' fixed point, statistics, the E-step
-#include "engine_capi.hpp"        // the C ABI of include/smcpp_engine.h
+#include "engine_products.hpp"    // products of the stored vectors of an E-step (posterior, loglik track, score track) and simulation: host side + entry points
+#include "engine_capi.hpp"        // the C ABI of include/smcpp_engine.h: create / destroy, setters, E-step, Q, getters, statistics packing
 #include "engine_rccl.hpp"        // the engine-issued exchange through RCCL's C API (opt-in)
 #include "engine_hostapi.hpp"     // host-only and debug exports used by the test-suite
 #include "shaping.hpp"            // SURVEY.md 8 f-2 on the device: thin_data / bin_observations / compress_repeated_obs (integer, HBM-bound)

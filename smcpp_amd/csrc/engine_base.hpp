@@ -3,6 +3,13 @@
 using namespace smcpp_dev;
 
 static thread_local std::string g_err;
+// every entry point of the C ABI: 0, or 1 with the message in g_err (smcpp_last_error)
+#define API_BEGIN try {
+#define API_END                                                                    \
+    return 0;                                                                      \
+    }                                                                              \
+    catch (const std::exception &e) { g_err = e.what(); return 1; }               \
+    catch (...) { g_err = "unknown error"; return 1; }
 
 // Logger::logger_cb (src/common.cpp:35-40, _smcpp.pxd:26): messages of the engine go to the binding's callback
 typedef void (*smcpp_logger_cb_t)(const char *name, const char *level, const char *message);

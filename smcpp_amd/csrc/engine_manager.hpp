@@ -223,9 +223,16 @@ struct smcpp_im {
     struct PostSource { const double *rows, *g0; int L; };
     PostSource post_source(int c);                // (after the argument checks: may launch k_gamma_merge)
     void post_columns(int c, long long start, long long stop, long long step, bool normalize, bool f32, void *out, double *colsum);
-    // posterior transition products (posterior_trans_dev.hpp, smcpp_posterior_transition*): the generators of the last E-step's T, the
-    // wavefronts' scratch (parked addends, checkpoints of long rows), the products per engine row and per selected caller's row
-    DevBuf<double> d_pt_gen, d_pt_ckpt, d_pt_eng, d_pt_sel;
+    // what the product calls share (engine_products.hpp): the generators of the last E-step's T on the device (constants of the
+    // E-step, uploaded by every walking call), the host-side set-up of a walk over the stored vectors
+    DevBuf<double> d_walk_gen;
+    SsArgs walk_generators();                     // ss_gen -> d_walk_gen on `stream`; a fresh SsArgs with M, Mp and the generators set
+    int longest_row(int c);                       // the longest engine row of contig c
+    long long walk_slots() const;                 // wavefront slots of a persistent walk
+    const long long *user_prefix_dev(int c);      // user_prefix[c] on the device, uploaded on first use
+    // posterior transition products (posterior_trans_dev.hpp, smcpp_posterior_transition*): the wavefronts' scratch (parked addends,
+    // checkpoints of long rows), the products per engine row and per selected caller's row
+    DevBuf<double> d_pt_ckpt, d_pt_eng, d_pt_sel;
     DevBuf<float> d_pt_park;
     const int *piece_first_dev(int c);            // first piece of every caller's row of contig c on the device; nullptr: no row is cut
     void post_transitions_check();                // throws unless the stored vectors and a structured T are there
@@ -266,7 +273,7 @@ struct smcpp_im {
     void post_positions_grid(int c, long long pos0, long long pos1, long long step);     // -> pq_items (host)
     void post_positions_segments(int c, long long W);                                    // -> pq_items, pq_start, pq_nseg (host)
     void post_positions_scratch_check(size_t extra_bytes);                               // throws beyond the 1 GiB cap
-    const double *post_colsum(int c, const PostSource &src);                             // [Lu + 1] column sums on the device
+    const double *post_colsum(int c, const PostSource &src, DevBuf<double> &dst);        // [Lu + 1] column sums on the device, in dst
     void post_positions_launch(int c, int kind, PqArgs &pa);
     // log-likelihood track (loglik_track_dev.hpp, smcpp_loglik_rows / _positions / _windows): buffers of its own - the posterior
     // products' are neither read nor written.  The position prefix of the ENGINE's rows per contig (where rows are cut; otherwise the
@@ -274,7 +281,7 @@ struct smcpp_im {
     std::vector<DevBuf<long long>> d_ll_epos;
     std::vector<LlItem> ll_items;
     DevBuf<LlItem> d_ll_items;
-    DevBuf<double> d_ll_gen, d_ll_part, d_ll_pre, d_ll_out, d_ll_bnd, d_ll_ratio;
+    DevBuf<double> d_ll_part, d_ll_pre, d_ll_out, d_ll_bnd, d_ll_ratio;
     std::vector<double> ll_ratio_h;
     long long ll_nslots = 0;                      // slots the items of the last table write
     int ll_waves = 0;                             // wavefronts of the last walk (smcpp_describe)
@@ -287,7 +294,7 @@ struct smcpp_im {
     // score track (score_track_dev.hpp, smcpp_score_rows / _windows): buffers of its own - the posterior products' and the loglik
     // track's are neither read nor written.  The tables G_pi | dT | G_E of the last E-step's parameters (built from the host Jacobians
     // on the first call behind an E-step), the checkpoints of long rows, the parts per engine row, per selected caller's row, the
-    // windows (the generators travel in the transition products' d_pt_gen: constants of the E-step, uploaded by every walking call)
+    // windows (the generators travel in d_walk_gen, as for every walking call)
     DevBuf<double> d_sc_tab, d_sc_ckpt, d_sc_eng, d_sc_sel, d_sc_out;
     bool sc_tab_valid = false;                    // d_sc_tab belongs to the last E-step (cleared by estep())
     int sc_waves = 0;                             // wavefronts of the last score call (smcpp_describe)

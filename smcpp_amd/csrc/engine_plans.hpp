@@ -397,6 +397,25 @@ void smcpp_im::run_chains() {
 // ---------------------------------------------------------------------------------------------------------------
 // chains on the semiseparable structure of T (chains_ss.hpp)
 // ---------------------------------------------------------------------------------------------------------------
+// The generator arrays lie side by side, gen = [10][MS] in the order f_dc f_g f_cg f_b f_a f_d b_dc b_g b_b b_a, the backward ones
+// mirrored (state j at MS - 1 - j): written on the host by ss_pack_generators, handed to a kernel by set_generators.
+static void ss_pack_generators(int M, int MS, double c0, const std::vector<double> &d, const std::vector<double> &g,
+                               const std::vector<double> &a, const std::vector<double> &b, std::vector<double> &gen) {
+    gen.assign((size_t)10 * MS, 0.0);
+    double *f = &gen[0], *bw = f + (size_t)6 * MS;
+    for (int j = 0; j < M; ++j) {
+        f[j] = d[j] - c0; f[MS + j] = g[j]; f[2 * MS + j] = c0 - g[j]; f[3 * MS + j] = b[j]; f[4 * MS + j] = a[j]; f[5 * MS + j] = d[j];
+        const int p = MS - 1 - j;
+        bw[p] = d[j] - c0; bw[MS + p] = g[j]; bw[2 * MS + p] = b[j]; bw[3 * MS + p] = a[j];
+    }
+}
+// Points the ten generator arrays of `a` at gd (gen on the device) and sets c0.
+static void set_generators(SsArgs &a, const double *gd, int MS, double c0) {
+    a.f_dc = gd; a.f_g = gd + MS; a.f_cg = gd + 2 * MS; a.f_b = gd + 3 * MS; a.f_a = gd + 4 * MS; a.f_d = gd + 5 * MS;
+    a.b_dc = gd + 6 * MS; a.b_g = gd + 7 * MS; a.b_b = gd + 8 * MS; a.b_a = gd + 9 * MS;
+    a.c0 = c0;
+}
+
 // Generators of T = diag(d) + [below: g_j] + [above: c0 + Phi'(i,j)], Phi'(i,i+1) = b_i, Phi'(i,j+1) = a_j Phi'(i,j)
 // (transition.cpp:176-254; c0 = 1e-5 / (M + 1) is the mixing constant of lines 249-254).  The dense T is what the reference's
 // getters hand out and what the statistics use, so the generators are taken FROM it and the reconstruction is checked entry by
@@ -441,14 +460,7 @@ static bool ss_generators(int M, int MS, const double *Tm, std::vector<double> &
     for (int j = 0; j < M; ++j)
         if (!(d[j] > 0.0) || !std::isfinite(a[j]) || !std::isfinite(b[j])) return false;
     c0_out = c0;
-    gen.assign((size_t)10 * MS, 0.0);
-    double *f_dc = &gen[0], *f_g = f_dc + MS, *f_cg = f_g + MS, *f_b = f_cg + MS, *f_a = f_b + MS, *f_d = f_a + MS,
-           *b_dc = f_d + MS, *b_g = b_dc + MS, *b_b = b_g + MS, *b_a = b_b + MS;
-    for (int j = 0; j < M; ++j) {
-        f_dc[j] = d[j] - c0; f_g[j] = g[j]; f_cg[j] = c0 - g[j]; f_b[j] = b[j]; f_a[j] = a[j]; f_d[j] = d[j];
-        const int p = MS - 1 - j;
-        b_dc[p] = d[j] - c0; b_g[p] = g[j]; b_b[p] = b[j]; b_a[p] = a[j];
-    }
+    ss_pack_generators(M, MS, c0, d, g, a, b, gen);
     return true;
 }
 
@@ -472,14 +484,7 @@ static bool ss_generators_from_tgen(int M, int MS, const smcpp_host::TransitionG
     for (int j = 0; j < M; ++j)
         if (!(d[j] > 0.0) || !std::isfinite(a[j]) || !std::isfinite(b[j]) || !(b[j] >= 0.0) || (j + 1 < M && !(g[j] > 0.0))) return false;
     c0_out = c0;
-    gen.assign((size_t)10 * MS, 0.0);
-    double *f_dc = &gen[0], *f_g = f_dc + MS, *f_cg = f_g + MS, *f_b = f_cg + MS, *f_a = f_b + MS, *f_d = f_a + MS,
-           *b_dc = f_d + MS, *b_g = b_dc + MS, *b_b = b_g + MS, *b_a = b_b + MS;
-    for (int j = 0; j < M; ++j) {
-        f_dc[j] = d[j] - c0; f_g[j] = g[j]; f_cg[j] = c0 - g[j]; f_b[j] = b[j]; f_a[j] = a[j]; f_d[j] = d[j];
-        const int p = MS - 1 - j;
-        b_dc[p] = d[j] - c0; b_g[p] = g[j]; b_b[p] = b[j]; b_a[p] = a[j];
-    }
+    ss_pack_generators(M, MS, c0, d, g, a, b, gen);
     return true;
 }
 
@@ -580,10 +585,7 @@ void smcpp_im::ss_launch_initial() {
     a.chunks = d_chunks.p; a.rowdesc = d_rowdesc_ss.p + ROWDESC_PAD;
     a.chunks_b = d_chunks_b.p; a.nchunks_b = (int)chunks_b.size(); a.tasks = d_tasks.p;
     a.pi_f = reinterpret_cast<const float *>(put(pi_f.data(), pi_f.size() * 4));
-    const double *gd = reinterpret_cast<const double *>(put(ss_gen.data(), ss_gen.size() * 8));
-    a.f_dc = gd; a.f_g = gd + MS; a.f_cg = gd + 2 * MS; a.f_b = gd + 3 * MS; a.f_a = gd + 4 * MS; a.f_d = gd + 5 * MS;
-    a.b_dc = gd + 6 * MS; a.b_g = gd + 7 * MS; a.b_b = gd + 8 * MS; a.b_a = gd + 9 * MS;
-    a.c0 = ss_c0;
+    set_generators(a, reinterpret_cast<const double *>(put(ss_gen.data(), ss_gen.size() * 8)), MS, ss_c0);
     if (E_on_dev) a.E = dprep->d_Es.p;       // written by the device preparation, by key slot
     else {
         const size_t eoff = (off + 255) & ~(size_t)255;
@@ -1055,10 +1057,7 @@ void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
         }
         SsArgs sa = SsArgs();
         sa.M = M; sa.Mp = Mp;
-        const double *gd = d_gp_gen.p;
-        sa.f_dc = gd; sa.f_g = gd + MS; sa.f_cg = gd + 2 * MS; sa.f_b = gd + 3 * MS; sa.f_a = gd + 4 * MS; sa.f_d = gd + 5 * MS;
-        sa.b_dc = gd + 6 * MS; sa.b_g = gd + 7 * MS; sa.b_b = gd + 8 * MS; sa.b_a = gd + 9 * MS;
-        sa.c0 = ss_c0;
+        set_generators(sa, d_gp_gen.p, MS, ss_c0);
         const int nw = (int)std::min<size_t>(npc, 4096);
         d_gpark.alloc((size_t)nw * 64 * MS);
         const dim3 grid(ceil_div(nw, 4)), block(256);

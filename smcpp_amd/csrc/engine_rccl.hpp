@@ -321,10 +321,7 @@ static int ss_debug_apply(int M, const double *T, int nvec, const double *x, con
     df.alloc(hx.size()); db.alloc(hx.size());
     SsArgs a = SsArgs();
     a.M = M;
-    const double *gd = dg.p;
-    a.f_dc = gd; a.f_g = gd + MS; a.f_cg = gd + 2 * MS; a.f_b = gd + 3 * MS; a.f_a = gd + 4 * MS; a.f_d = gd + 5 * MS;
-    a.b_dc = gd + 6 * MS; a.b_g = gd + 7 * MS; a.b_b = gd + 8 * MS; a.b_a = gd + 9 * MS;
-    a.c0 = c0;
+    set_generators(a, dg.p, MS, c0);
     if (float_scans && M <= 32) hipLaunchKernelGGL((k_ss_apply<1, true, true>), dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec);
     else if (float_scans) hipLaunchKernelGGL((k_ss_apply<1, true, false>), dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec);
     else switch (NPL) {

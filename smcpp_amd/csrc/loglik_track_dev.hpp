@@ -1,6 +1,6 @@
 // loglik_track_dev.hpp - the log-likelihood TRACK of the last E-step: l(p) = log P(o_1 .. o_p) per caller's row, per position of a
 // grid and per window ("Log-likelihood track").  Included from engine.hip behind posterior_pos_dev.hpp; the host side is
-// in engine_capi.hpp (smcpp_loglik_rows / _positions / _windows).  Forward quantities only: the stored float alpha and log c of
+// in engine_products.hpp (smcpp_loglik_rows / _positions / _windows).  Forward quantities only: the stored float alpha and log c of
 // every engine row, which every E-step leaves behind - save_gamma is not needed, and the posterior buffers are not touched.
 //
 // Positions 0 .. N of a contig (0 = column 0; engine row r covers the `span` positions behind EP[r - 1], EP = the position prefix

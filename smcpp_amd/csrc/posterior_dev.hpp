@@ -1,5 +1,5 @@
 // posterior_dev.hpp - products of the per-row posteriors of the last save_gamma E-step, computed where the rows lie (DESIGN.md,
-// "Posterior products on the device").  Included from engine.hip; the host side is in engine_capi.hpp (smcpp_posterior_*).
+// "Posterior products on the device").  Included from engine.hip; the host side is in engine_products.hpp (smcpp_posterior_*).
 //
 // Source of every kernel: `rows` [L + 1][Mp] fp64, one row per caller's row (d_gamma_rows of the contig, or merged_gamma(c) where long
 // rows were cut), states contiguous; row 0 of that block is unset: column 0 is `g0` [Mp] (gamma0 of the contig).  The padding states

@@ -1,6 +1,6 @@
 // posterior_paths_dev.hpp - joint draws of the hidden-state path from the posterior of the last save_gamma E-step, by forward
 // filtering and backward sampling ("Posterior paths").  Included from engine.hip behind posterior_trans_dev.hpp (whose
-// row walk - blocks of 64 positions, fp64 checkpoints of long rows - is repeated here); the host side is in engine_capi.hpp
+// row walk - blocks of 64 positions, fp64 checkpoints of long rows - is repeated here); the host side is in engine_products.hpp
 // (smcpp_posterior_sample_rows / _sample_positions).
 //
 // Positions 0 .. N of a contig (0 = column 0, engine row r covers the `span` positions behind the end of row r - 1), forward vectors

@@ -1,7 +1,7 @@
 // posterior_trans_dev.hpp - posterior TRANSITION products of the last save_gamma E-step: per row and per window the expected number of
 // positions at which the hidden state stays, moves up (to a higher index = older state) or moves down ("Posterior
 // transition products").  Included from engine.hip behind chains_ss.hpp (the scan steps) and posterior_dev.hpp (PostSel); the host
-// side is in engine_capi.hpp (smcpp_posterior_transitions / _transition_windows).
+// side is in engine_products.hpp (smcpp_posterior_transitions / _transition_windows).
 //
 // For a position p of a row with emission vector e, forward vector x_{p-1} before it and backward vector y_p after it,
 //     xi_p(i, j) = x_{p-1}(i) T(i, j) e(j) y_p(j) / Z_p,     stay = sum_i xi(i, i),  up = sum_{i<j} xi(i, j),  down = sum_{i>j} xi(i, j).

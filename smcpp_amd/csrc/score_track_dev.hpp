@@ -1,7 +1,7 @@
 // score_track_dev.hpp - the SCORE track of the last save_gamma E-step: per row and per window the derivative of the log-likelihood
 // with respect to every seeded direction of the model ("Score track").  Included from engine.hip behind
 // posterior_trans_dev.hpp (pt_add, pt_fwd_addends, the blocked walk this one follows) and posterior_dev.hpp (PostSel); the host side
-// is in engine_capi.hpp (smcpp_score_rows / _windows).
+// is in engine_products.hpp (smcpp_score_rows / _windows).
 //
 // For a position p of a row with key k, emission vector e = E[k], forward vector x_{p-1} before it and backward vector y_p after it,
 //     xi_p(i, j) = x_{p-1}(i) T(i, j) e(j) y_p(j) / Z_p,     gamma_p(j) = sum_i xi_p(i, j),

@@ -1,6 +1,6 @@
 // simulate_dev.hpp - draws of (hidden path, observations) from the model itself: the forward process whose marginal likelihood the
 // E-step computes ("Simulation").  Included from engine.hip behind the posterior headers (pp_uniform, ss_scan, dpp0 and
-// lane_get come from there); the host side is smcpp_simulate in engine_capi.hpp, the contract is in include/smcpp_engine.h.
+// lane_get come from there); the host side is smcpp_simulate in engine_products.hpp, the contract is in include/smcpp_engine.h.
 //
 // Positions 0 .. N; x_0 ~ pi, x_p ~ T(x_{p-1}, .), o_p ~ Ebar(. | x_p) over the caller's alphabet.  The walk is by EVENTS: from
 // (p, i) a geometric number G of quiet positions (state kept, quiet key emitted; P(G >= g) = s_i^g, s_i = T(i, i) Ebar(q | i)) is
