@@ -392,6 +392,7 @@ struct smcpp_im {
     int llblk = 64;
     int ZS = 8;
     int ZG = 1;                          // shares of the per-key gamma-sum reduction of the one-pass span-1 form (a hot key holds most slabs)
+    int slab_rows_1 = 0, slab_rows_e = 0;   // rows per span-1 rank slab / per span > 1 slab as make_slabs cut them (smcpp_describe)
     int max_pass = 0;
     int last_fwd_passes = 0, last_bwd_passes = 0;
     float eps_f = 2e-6f;
@@ -1070,6 +1071,7 @@ void smcpp_im::make_slabs() {
     int S_EG = (int)std::max<long long>(slab_rows, (ne + target - 1) / target);
     S_EG = (S_EG + 15) / 16 * 16;
     const int S_SC = 256;
+    slab_rows_1 = S_RK; slab_rows_e = S_EG;
     for (int c = 0; c < n_contigs; ++c) {
         const long long base = contig_base[c];
         // ---- span-1 rows sorted by key ----

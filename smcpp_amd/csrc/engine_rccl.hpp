@@ -255,9 +255,10 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
                  ", \"statistics\": {\"span_gt1_stream\": \"%s\", \"span1_stream\": \"%s\", \"gamma_sums_stream\": \"%s\", "
                  "\"loglik_stream\": \"%s\", \"per_row_gamma_stream\": \"%s\", \"span1_form\": \"%s\", \"rank_update\": \"%s\", "
                  "\"eigen\": \"%s\", \"span_gt1_rank_early\": %s, \"gamma_sums_reduced\": \"%s\", \"per_row_gamma\": \"%s\", "
-                 "\"per_row_gamma_beside\": %s}",
+                 "\"per_row_gamma_beside\": %s, \"slab_rows_span1\": %d, \"slab_rows_span_gt1\": %d, \"reduction_shares\": %d}",
                  stream[p.span_gt1], stream[p.span1], stream[p.gsum], stream[p.loglik], stream[p.gamma], p.s1_one_pass ? "one pass" : "two kernels",
-                 rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false");
+                 rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false",
+                 im->slab_rows_1, im->slab_rows_e, im->ZS);
         s += p.resolved ? t : ", \"statistics\": null";
         // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
         static const char *const route[] = {"none", "device", "host"};

@@ -56,7 +56,11 @@ ROUTES = pytest.mark.parametrize("route", ["raw", "params"])
 
 def _check_stats_plan(im, **want):
     """The arrangement of the statistics phase the E-step ran (describe()["statistics"]): what the size rules pick for this input."""
-    got = im.describe()["statistics"]
+    got = dict(im.describe()["statistics"])
+    # (the slab plan make_slabs cut: span-1 rank slabs in groups of 4 rows, span > 1 slabs in batches of 16, at least the 128 rows of
+    # the default; 8 .. 16 shares per reduction range.  tests/test_gpu_stats_edges.py places their edges.)
+    s1, se, zs = (got.pop(k) for k in ("slab_rows_span1", "slab_rows_span_gt1", "reduction_shares"))
+    assert s1 >= 128 and s1 % 4 == 0 and se >= 128 and se % 16 == 0 and 8 <= zs <= 16, (s1, se, zs)
     assert got == dict(dict(loglik_stream="third", rank_update="teams", eigen="fold on the scans", per_row_gamma="none",
                             per_row_gamma_stream="main", per_row_gamma_beside=False), **want), got
 
