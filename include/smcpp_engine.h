@@ -196,6 +196,18 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap);
 int smcpp_debug_ss_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b);
 /* ... the same position by the step of the stored passes with every scan in float (M <= 64; the M <= 32 form when M <= 32). */
 int smcpp_debug_ss_apply_float_scans(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b);
+/* ... and by every compiled form of the step (tests/test_gpu_ss_step.py), the production device functions on caller vectors:
+ *   form 0  fp64 scans, 1 .. 16 states per lane (smcpp_debug_ss_apply)                                      M <= 1024
+ *   form 1  float scans of the stored passes as the engine picks them: the two-row form at M <= 32          M <= 64
+ *   form 2  float scans of the stored passes, full-width form also at M <= 32 (what SMCPP_SS_H32=0 runs)    M <= 64
+ *   form 3  the all-float step of the light passes and of the float halo, 1 .. 16 states per lane           M <= 1024
+ *   form 4  the all-float step, two-row form                                                                M <= 32
+ *   form 5  power jumps: the tables of the P-th power of the operator with e[0] as the jump key's emission vector (every row of e
+ *           should be that vector), then per vector out_f = A_f^k x, out_b = A_b^k x, A_f = diag(e) T^T, A_b = T diag(e);
+ *           `power` = k = P (one jump) or 3 P (three jumps), P = 4, 8 or 16                                    M <= 64
+ * `power` is 0 for the forms 0 .. 4.  A combination the engine never compiles is refused (1, smcpp_last_error) before any launch.
+ * Returns 2 when T has no semiseparable structure, 3 when a power jump left anything but 0.0 on a padded state (M < 64). */
+int smcpp_debug_ss_apply_form(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int form, int power);
 /* Host phase of the last E-step in milliseconds: [cold preparation A6-A10 (0 when the parameters were still fresh or
  * came from smcpp_set_raw), eigensystems, layouts + staging + copy enqueue, whole host phase] */
 int smcpp_last_host_timing(smcpp_im *im, double out[4]);

@@ -84,6 +84,7 @@ cdef extern from "smcpp_engine.h":
     int smcpp_describe(smcpp_im *im, char *buf, int cap) nogil
     int smcpp_debug_ss_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b) nogil
     int smcpp_debug_ss_apply_float_scans(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b) nogil
+    int smcpp_debug_ss_apply_form(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int form, int power) nogil
     int smcpp_last_host_timing(smcpp_im *im, double *out) nogil
     void *smcpp_stream(smcpp_im *im) nogil
     int smcpp_device(smcpp_im *im) nogil

@@ -2010,7 +2010,7 @@ __global__ __launch_bounds__(256) void k_gamma_rows_scan(SsArgs sa, GammaRowArgs
     }
 }
 
-// Unit-test entry (tests/test_gpu_ss.py through smcpp_debug_ss_apply): out_f = e o (T^T x), out_b = T (e o x) by the scans,
+// Unit-test entries (tests/test_gpu_ss.py, tests/test_gpu_ss_step.py through smcpp_debug_ss_apply / _form): out_f = e o (T^T x), out_b = T (e o x) by the scans,
 // one wavefront per vector.  MIX / H32: the all-float scans of the stored passes (one state per lane) and their M <= 32 form.
 template <int NPL, bool MIX = false, bool H32 = false>
 __global__ __launch_bounds__(64) void k_ss_apply(SsArgs a, const double *__restrict__ x, const double *__restrict__ e,
@@ -2037,6 +2037,60 @@ __global__ __launch_bounds__(64) void k_ss_apply(SsArgs a, const double *__restr
         const int p = lane * NPL + k, q = MS - 1 - p;
         out_f[(size_t)v * MS + p] = yf[k];
         out_b[(size_t)v * MS + q] = yb[k];
+    }
+}
+
+// ... the same position by the all-float step of the light passes and of the float halo (ss_fwd_step_f / ss_bwd_step_f; H32: their
+// two-row form, M <= 32).  The vector and the emission vector are rounded to float on the way in, as ss_forward_light / ss_emission_f do.
+template <int NPL, bool H32 = false>
+__global__ __launch_bounds__(64) void k_ss_apply_light(SsArgs a, const double *__restrict__ x, const double *__restrict__ e,
+                                                       double *__restrict__ out_f, double *__restrict__ out_b, int nvec) {
+    constexpr int MS = 64 * NPL;
+    const int lane = threadIdx.x, v = blockIdx.x;
+    if (v >= nvec) return;
+    SsLightC<NPL> cf, cb;
+    ss_load_light<NPL, false>(a, lane, cf);
+    ss_load_light<NPL, true>(a, lane, cb);
+    float xf[NPL], ef[NPL], xb[NPL], eb[NPL], yf[NPL], yb[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int p = lane * NPL + k, q = MS - 1 - p;
+        xf[k] = (float)x[(size_t)v * MS + p]; ef[k] = (float)e[(size_t)v * MS + p];
+        xb[k] = (float)x[(size_t)v * MS + q]; eb[k] = (float)e[(size_t)v * MS + q];
+    }
+    float S, Sw;
+    ss_fwd_step_f<NPL, H32>(cf, xf, ef, yf, S);
+    ss_bwd_step_f<NPL, H32>(cb, xb, eb, yb, Sw);
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int p = lane * NPL + k, q = MS - 1 - p;
+        out_f[(size_t)v * MS + p] = (double)yf[k];
+        out_b[(size_t)v * MS + q] = (double)yb[k];
+    }
+}
+
+// ... and the power jumps: the positions t = 1 .. span - 1 of a row of the jump key by ss_jump_run on the tables k_ss_jump_tables left
+// in a.jtab_f / a.jtab_t / a.jdiag (one state per lane): out_f = A^k x on the forward lanes, out_b = (A^T)^k x on the backward lanes
+// (lane l = state 63 - l), k = span - 1 rounded down to a multiple of a.jump.  ran[v] = the position ss_jump_run returned.
+__global__ __launch_bounds__(64) void k_ss_apply_jump(SsArgs a, const double *__restrict__ x, double *__restrict__ out_f,
+                                                      double *__restrict__ out_b, int *__restrict__ ran, int nvec, int span) {
+    const int lane = threadIdx.x, v = blockIdx.x;
+    if (v >= nvec) return;
+    int t;
+    {
+        SsJumpR j;
+        ss_jump_load<false>(a, lane, j);
+        float xf = (float)x[(size_t)v * 64 + lane];
+        t = ss_jump_run(j, xf, 1, span);
+        out_f[(size_t)v * 64 + lane] = (double)xf;
+    }
+    {
+        SsJumpR j;
+        ss_jump_load<true>(a, lane, j);
+        float xb = (float)x[(size_t)v * 64 + 63 - lane];
+        const int tb = ss_jump_run(j, xb, 1, span);
+        out_b[(size_t)v * 64 + 63 - lane] = (double)xb;
+        if (lane == 0) ran[v] = t == tb ? t : -1;
     }
 }
 

@@ -516,12 +516,15 @@ static void launch_chain_ss_tt(const SsArgs &a, int ntasks, size_t shm, hipStrea
     lds_limit_once<k_chain_ss<NPL_, HYB_, ALL_, H32_>>();
     hipLaunchKernelGGL((k_chain_ss<NPL_, HYB_, ALL_, H32_>), dim3(ntasks / wgw), dim3(64 * wgw), shm, s, a);
 }
+// M <= 32 with one state per lane, no hybrid rows and every key slot in LDS: the instantiation whose scans skip the level that would only
+// move zeros (SMCPP_SS_H32=0: the full-width form there too).  describe() reports it as "two_row_scans".
+static bool ss_two_row_scans(int npl, bool hyb, int K, int nlds, int Mp) {
+    return npl == 1 && !hyb && K <= nlds && Mp <= 32 && !opt().off(smcpp_opt::O_SS_H32);
+}
 template <int NPL_, bool HYB_>
 static void launch_chain_ss_t(const SsArgs &a, int ntasks, size_t shm, hipStream_t s, int wgw) {
     // every key slot in LDS (the usual case): the instantiation without the global path of the emission vectors
-    // (M <= 32 with one state per lane: the instantiation whose scans skip the level that would only move zeros)
-    const bool h32_off = opt().off(smcpp_opt::O_SS_H32);
-    if (NPL_ == 1 && !HYB_ && a.K <= a.nlds && a.Mp <= 32 && !h32_off) launch_chain_ss_tt<NPL_, HYB_, true, NPL_ == 1 && !HYB_>(a, ntasks, shm, s, wgw);
+    if (ss_two_row_scans(NPL_, HYB_, a.K, a.nlds, a.Mp)) launch_chain_ss_tt<NPL_, HYB_, true, NPL_ == 1 && !HYB_>(a, ntasks, shm, s, wgw);
     else if (a.K <= a.nlds) launch_chain_ss_tt<NPL_, HYB_, true>(a, ntasks, shm, s, wgw);
     else launch_chain_ss_tt<NPL_, HYB_, false>(a, ntasks, shm, s, wgw);
 }

@@ -225,13 +225,14 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
                  ", \"plan\": {\"chain_family\": %d, \"scan_chains\": %s, \"hybrid_rows\": %s, \"states\": %d, \"states_padded\": %d, "
                  "\"states_per_lane\": %d, \"keys\": %d, \"eigen_keys\": %d, \"rows\": %lld, \"positions\": %lld, \"max_span\": %d, "
                  "\"chunks_forward\": %zu, \"chunks_backward\": %zu, \"wavefronts_per_simd\": %d, \"halo_pass\": %s, "
-                 "\"light_passes_forward\": %d, \"light_passes_backward\": %d, \"float_scans_in_stored_passes\": %s, "
+                 "\"light_passes_forward\": %d, \"light_passes_backward\": %d, \"float_scans_in_stored_passes\": %s, \"two_row_scans\": %s, "
                  "\"passes_to_certificate\": %d, \"passes_launched\": %d, \"certificate_pass_launched_up_front\": %s, "
                  "\"save_gamma\": %s, \"eigen_free_statistics\": %s, \"per_row_gamma\": \"%s\", \"long_rows_cut\": %s, \"warm_start\": %s, \"host_threads\": %d",
                  fam, im->ss_static ? "true" : "false", im->ss_hybrid ? "true" : "false", im->M, im->Mp, im->NPL, im->K, im->Ke,
                  (long long)(im->total_rows - im->n_contigs), (long long)im->ss_positions, im->ss_max_span, im->chunks.size(),
                  im->chunks_b.size(), im->ss_wpc, (im->ss_static && im->ss_args.halo) ? "true" : "false", im->ss_light_f, im->ss_light_b,
-                 (im->ss_static && im->ss_args.mixed) ? "true" : "false", im->last_ss_passes, im->ss_launched,
+                 (im->ss_static && im->ss_args.mixed) ? "true" : "false",
+                 (im->ss_static && ss_two_row_scans(im->NPL, im->ss_hybrid, im->K, im->ss_nlds, im->Mp)) ? "true" : "false", im->last_ss_passes, im->ss_launched,
                  (opt().on(smcpp_opt::O_SS_CERT_PASS) || im->ss_need_cert_pass) ? "true" : "false", im->save_gamma ? "true" : "false",
                  im->eigfree ? "true" : "false", !im->save_gamma ? "none" : im->eigfree ? "scan steps" : im->stats_plan.gamma_form == StatsPlan::GAMMA_PIECES ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
                  im->warm_start ? "true" : "false", omp_get_max_threads());
@@ -289,25 +290,48 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
     return (int)s.size();
 }
 
-// Test hook (tests/test_gpu_ss.py): one position of both scan chains on nvec vectors, out_f = e o (T^T x), out_b = T (e o x);
-// x, e and the outputs are [nvec][M].  Returns 2 when T has no semiseparable structure.  float_scans != 0 (M <= 64): the step of
-// the stored passes with every scan in float (chains_ss.hpp: ss_x_scan_fwd / ss_x_scan_bwd; the M <= 32 form when M <= 32).
-static int ss_debug_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int float_scans);
+// Test hook (tests/test_gpu_ss.py, tests/test_gpu_ss_step.py): one position of both scan chains on nvec vectors, out_f = e o (T^T x),
+// out_b = T (e o x); x, e and the outputs are [nvec][M].  Returns 2 when T has no semiseparable structure.  `form` picks the compiled
+// form of the step (the table in include/smcpp_engine.h), `power` the positions a power jump crosses (form 5 only).
+static int ss_debug_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int form, int power);
 int smcpp_debug_ss_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b) {
     API_BEGIN
-    return ss_debug_apply(M, T, nvec, x, e, out_f, out_b, 0);
+    return ss_debug_apply(M, T, nvec, x, e, out_f, out_b, 0, 0);
     API_END
 }
 int smcpp_debug_ss_apply_float_scans(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b) {
     API_BEGIN
     if (M > 64) throw std::runtime_error("the all-float scans hold one state per lane: M <= 64");
-    return ss_debug_apply(M, T, nvec, x, e, out_f, out_b, 1);
+    return ss_debug_apply(M, T, nvec, x, e, out_f, out_b, 1, 0);
     API_END
 }
-static int ss_debug_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int float_scans) {
+int smcpp_debug_ss_apply_form(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int form, int power) {
+    API_BEGIN
+    return ss_debug_apply(M, T, nvec, x, e, out_f, out_b, form, power);
+    API_END
+}
+extern "C++" {
+template <int NPL_>
+static void ss_debug_launch(int form, const SsArgs &a, const double *x, const double *e, double *f, double *b, int nvec, hipStream_t s) {
+    if (form == 0) hipLaunchKernelGGL(k_ss_apply<NPL_>, dim3(nvec), dim3(64), 0, s, a, x, e, f, b, nvec);
+    else hipLaunchKernelGGL(k_ss_apply_light<NPL_>, dim3(nvec), dim3(64), 0, s, a, x, e, f, b, nvec);
+}
+}
+static int ss_debug_apply(int M, const double *T, int nvec, const double *x, const double *e, double *out_f, double *out_b, int form, int power) {
     {
+    // every combination the engine never compiles is refused before anything is launched
+    if (M < 1 || M > 1024) throw std::runtime_error("unsupported number of hidden states");
+    if (nvec < 1 || !T || !x || !e || !out_f || !out_b) throw std::runtime_error("smcpp_debug_ss_apply: no vectors");
+    if (form < 0 || form > 5) throw std::runtime_error("smcpp_debug_ss_apply_form: form must be 0 .. 5");
+    if ((form == 1 || form == 2) && M > 64) throw std::runtime_error("the all-float scans hold one state per lane: M <= 64");
+    if (form == 4 && M > 32) throw std::runtime_error("the two-row form of the light step holds the live states in two 16-lane rows: M <= 32");
+    if (form == 5 && M > 64) throw std::runtime_error("power jumps hold one state per lane: M <= 64");
+    int P = 0;
+    if (form == 5) {
+        for (int q : {4, 8, 16}) if (power == q || power == 3 * q) P = q;
+        if (!P) throw std::runtime_error("power jumps are compiled for the powers 4, 8 and 16: `power` must be P or 3 P");
+    } else if (power != 0) throw std::runtime_error("smcpp_debug_ss_apply_form: `power` belongs to form 5");
     const int NPL = M > 512 ? 16 : M > 256 ? 8 : (M + 63) / 64, MS = 64 * NPL;
-    if (M > 1024) throw std::runtime_error("unsupported number of hidden states");
     std::vector<double> gen;
     double c0 = 0.0;
     if (!ss_generators(M, MS, T, gen, c0)) return 2;
@@ -323,20 +347,44 @@ static int ss_debug_apply(int M, const double *T, int nvec, const double *x, con
     SsArgs a = SsArgs();
     a.M = M;
     set_generators(a, dg.p, MS, c0);
-    if (float_scans && M <= 32) hipLaunchKernelGGL((k_ss_apply<1, true, true>), dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec);
-    else if (float_scans) hipLaunchKernelGGL((k_ss_apply<1, true, false>), dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec);
+    const double *px = dx.p, *pe = de.p;
+    DevBuf<float> dtab;
+    DevBuf<double> ddiag;
+    DevBuf<int> dran;
+    if (form == 5) {
+        // the tables by the production kernel, from the FIRST emission vector as the jump key's (key slot 0 of a.E), as
+        // ss_launch_initial launches it; then the production load and run per vector
+        dtab.alloc(2 * 64 * 64); ddiag.alloc(64); dran.alloc(nvec);
+        a.E = pe; a.K = 1;
+        a.jump = P; a.jtab_f = dtab.p; a.jtab_t = dtab.p + 64 * 64; a.jdiag = ddiag.p;
+        hipLaunchKernelGGL(k_ss_jump_tables, dim3(16), dim3(256), 0, s, a, 0, dtab.p, dtab.p + 64 * 64, ddiag.p);
+        hipLaunchKernelGGL(k_ss_apply_jump, dim3(nvec), dim3(64), 0, s, a, px, df.p, db.p, dran.p, nvec, 1 + power);
+    } else if (form == 1 || form == 2) {
+        if (form == 1 && M <= 32) hipLaunchKernelGGL((k_ss_apply<1, true, true>), dim3(nvec), dim3(64), 0, s, a, px, pe, df.p, db.p, nvec);
+        else hipLaunchKernelGGL((k_ss_apply<1, true, false>), dim3(nvec), dim3(64), 0, s, a, px, pe, df.p, db.p, nvec);
+    } else if (form == 4) hipLaunchKernelGGL((k_ss_apply_light<1, true>), dim3(nvec), dim3(64), 0, s, a, px, pe, df.p, db.p, nvec);
     else switch (NPL) {
-        case 1: hipLaunchKernelGGL(k_ss_apply<1>, dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec); break;
-        case 2: hipLaunchKernelGGL(k_ss_apply<2>, dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec); break;
-        case 3: hipLaunchKernelGGL(k_ss_apply<3>, dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec); break;
-        case 4: hipLaunchKernelGGL(k_ss_apply<4>, dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec); break;
-        case 8: hipLaunchKernelGGL(k_ss_apply<8>, dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec); break;
-        default: hipLaunchKernelGGL(k_ss_apply<16>, dim3(nvec), dim3(64), 0, s, a, (const double *)dx.p, (const double *)de.p, df.p, db.p, nvec); break;
+        case 1: ss_debug_launch<1>(form, a, px, pe, df.p, db.p, nvec, s); break;
+        case 2: ss_debug_launch<2>(form, a, px, pe, df.p, db.p, nvec, s); break;
+        case 3: ss_debug_launch<3>(form, a, px, pe, df.p, db.p, nvec, s); break;
+        case 4: ss_debug_launch<4>(form, a, px, pe, df.p, db.p, nvec, s); break;
+        case 8: ss_debug_launch<8>(form, a, px, pe, df.p, db.p, nvec, s); break;
+        default: ss_debug_launch<16>(form, a, px, pe, df.p, db.p, nvec, s); break;
     }
     HIPCHK(hipGetLastError());
     std::vector<double> hf(hx.size()), hb(hx.size());
     HIPCHK(hipMemcpy(hf.data(), df.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hb.data(), db.p, hb.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (form == 5) {
+        // every jump ran (the walk stands at the row's last position), and a padded state receives exactly nothing
+        std::vector<int> ran(nvec);
+        HIPCHK(hipMemcpy(ran.data(), dran.p, ran.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int v = 0; v < nvec; ++v)
+            if (ran[v] != 1 + power) throw std::runtime_error("smcpp_debug_ss_apply_form: ss_jump_run stopped at position " + std::to_string(ran[v]));
+        for (int v = 0; v < nvec; ++v)
+            for (int j = M; j < MS; ++j)
+                if (hf[(size_t)v * MS + j] != 0.0 || hb[(size_t)v * MS + j] != 0.0) return 3;
+    }
     for (int v = 0; v < nvec; ++v) {
         std::memcpy(out_f + (size_t)v * M, &hf[(size_t)v * MS], sizeof(double) * M);
         std::memcpy(out_b + (size_t)v * M, &hb[(size_t)v * MS], sizeof(double) * M);
