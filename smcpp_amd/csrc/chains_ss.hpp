@@ -440,16 +440,45 @@ __device__ __forceinline__ void ss_bwd_step(const SsBwdC<NPL> &c, const double (
     }
 }
 
-// A block of 64 row descriptors has just been requested (one per lane): make the wavefront wait for it HERE, once per 64 rows.
-// Left pending, the load is carried around the row loop in registers, and the compiler - which cannot count how many stores the
-// rows in between have issued on the path it came by - puts an s_waitcnt vmcnt(0) at the head of EVERY row: with one wavefront
-// per SIMD that parks the chain until the alpha / beta row it has just stored is acknowledged by L2 (rocprofv3, round 4:
-// SQ_WAIT_ANY = 34 % of the wave cycles of this kernel).
-__device__ __forceinline__ void ss_desc_settle(int2 &d) { asm volatile("" : "+v"(d.x), "+v"(d.y)); }
-// ... and for the same reason every load issued BEFORE the row loop (generators, start vector, first descriptors) is waited for at
-// the loop's door: a constant first used inside the loop, behind a store, costs an s_waitcnt vmcnt(0) per row otherwise.
-// (gfx9 encoding of s_waitcnt: vmcnt(0), expcnt and lgkmcnt left at their maxima)
-__device__ __forceinline__ void ss_vm_drain() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+// The row descriptors a wavefront walks are the same in every lane, so they travel through the SCALAR path (round 7): one 8-byte
+// scalar load per row from the constant address space, two rows ahead of the row that is walked, into three rotating scalar pairs -
+// d0 (this row: span, flags, eigen key, floor), d1 (the next row: the key slot of the emission vector to fetch), d2 (on its way).
+// A scalar load counts on lgkmcnt like the LDS read of the emission vector and never on vmcnt: the row loop neither waits for the
+// alpha / beta row it has just stored (a vector load carried around the loop costs an s_waitcnt vmcnt(0) per row or, fetched 64
+// rows at a time, per refill: SQ_WAIT_ANY was 34 % of the wave cycles in round 4) nor spends v_readlane issue slots on taking the
+// row's fields out of a vector register.  ROWDESC_PAD (engine_base.hpp) covers the two rows read past either end of a contig; they
+// are fetched, never consumed.
+typedef int ss_desc_t __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(4))) ss_desc_t *SsDescStream;
+__device__ __forceinline__ SsDescStream ss_desc_stream(const int2 *p) { return (SsDescStream)(unsigned long long)p; }
+// The descriptors of a walk's first two rows (DIR = 1: forward walk from `p` upwards, -1: backward walk from `p` downwards); `p` is
+// left on the third, the next one to request.
+template <int DIR>
+__device__ __forceinline__ void ss_desc_first(SsDescStream &p, ss_desc_t &d1, ss_desc_t &d2) {
+    d1 = p[0]; d2 = p[DIR];
+    p += 2 * DIR;
+}
+// The request for the descriptor two rows on, made on entering a row.  Scalar loads return out of order, so what a row waits for at
+// its head - the descriptor requested a row ago, `arrived`, whose key slot addresses the LDS read of the next emission vector - is
+// lgkmcnt(0): a request scheduled in front of that wait would be waited for at once.  The empty statement ties the address to the
+// value that has arrived, so the request goes out behind the wait and has the whole row to land.  The scheduler promises nothing
+// about that placement, and the hoisted form computes the same and only runs slower: after a change of toolchain read the row heads
+// of k_chain_ss<1, false, true, false> again (tools/isa_mix.py disassembles it) - one s_load_dwordx2 per row, behind the
+// s_waitcnt lgkmcnt(0), in front of the ds_read of the next emission vector.
+template <int DIR>
+__device__ __forceinline__ ss_desc_t ss_desc_fetch(SsDescStream &p, int arrived) {
+    asm volatile("" : "+s"(p) : "s"(arrived));
+    const ss_desc_t d = p[0];
+    p += DIR;
+    return d;
+}
+// Every VECTOR load issued BEFORE the row loop (generators, start vector) is waited for at the loop's door: a constant first used
+// inside the loop, behind a store, costs an s_waitcnt vmcnt(0) per row otherwise - the compiler cannot count how many stores the
+// rows in between have issued on the path it came by.  The scalar side is drained with it: a scalar result still pending at the
+// door (the clock reads of SMCPP_DEBUG_CYCLES) makes the first scalar write to its register inside the loop an s_waitcnt lgkmcnt(0)
+// - a wait for nothing, until a descriptor request is in flight in front of it on every row.
+// (gfx9 encoding of s_waitcnt: vmcnt(0) and lgkmcnt(0), expcnt left at its maximum)
+__device__ __forceinline__ void ss_vm_drain() { __builtin_amdgcn_s_waitcnt(0x0070); }
 // A wavefront owns ONE chunk: its descriptor is the same in every lane, but it arrives through per-lane loads (the chunk index comes
 // from the thread index), so the compiler treats the row loop's trip count as divergent and wraps every iteration in exec-mask
 // bookkeeping (s_and_saveexec / s_andn2 exec / v_cmp against a vector register: a dozen scalar instructions per row).  Moved to
@@ -816,10 +845,10 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
     }
     SsFwdC<NPL> cst;
     ss_load_fwd<NPL>(a, lane, cst);
-    const int2 *rd = a.rowdesc + ch.base + rbeg + 1;           // descriptor of iteration j (row ell = rbeg + 1 + j)
+    SsDescStream rd = ss_desc_stream(a.rowdesc + ch.base + rbeg + 1);   // the walk's first descriptor: iteration j is row ell = rbeg + 1 + j
     const int nrows = ch.r1 - rbeg;
-    int2 dcur = rd[lane], dnxt = rd[64 + lane];
-    ss_desc_settle(dcur); ss_desc_settle(dnxt);
+    ss_desc_t d1, d2;
+    ss_desc_first<1>(rd, d1, d2);
     float *arow = a.alpha + (size_t)(ch.base + rbeg) * Mp;     // row ell - 1 of iteration j is arow + j Mp
     double *crow = a.cnorm + ch.base + rbeg;
     // MIX: the row's address advances by Mp floats per iteration (a 64-bit multiply per row otherwise), and the normalisers - float
@@ -833,7 +862,7 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
         if (jj <= jhi && jj > jst && jj > 0) crow[jj] = (double)__builtin_bit_cast(float, cacc);
     };
     double e[NPL];
-    ss_emission<NPL, false, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    ss_emission<NPL, false, ALLLDS>(a, sE, d1.x & 0xFFFF, lane, e);
     constexpr bool hyb = HYB && NPL == 1;
     const double *tab = sE + (size_t)a.nlds * MS;
     SsEigC ec;
@@ -850,14 +879,16 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
         const int jl = j & 63;
-        const int span = __builtin_amdgcn_readlane(dcur.y, jl);
-        const int ekr = (__builtin_amdgcn_readlane(dcur.x, jl) >> 16) & 0xFF;
-        const float flo = NPL >= 2 ? ss_floor_of<NPL>(__builtin_amdgcn_readlane(dcur.x, jl)) : 1e-10f;   // floor of the vector stored where this row begins
+        // this row's descriptor, the next row's, and the request for the one behind it
+        const ss_desc_t d0 = d1;
+        d1 = d2; d2 = ss_desc_fetch<1>(rd, d1.x);
+        const int span = d0.y;
+        const int ekr = (d0.x >> 16) & 0xFF;
+        const float flo = NPL >= 2 ? ss_floor_of<NPL>(d0.x) : 1e-10f;   // floor of the vector stored where this row begins
         npos += span;
-        // descriptor / emission vector of the next row
-        if (jl == 63) { dcur = dnxt; dnxt = rd[j + 65 + lane]; ss_desc_settle(dnxt); }
         if (MIX && jl == 0 && j > 0) cflush(j - 1);
-        const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
+        // emission vector of the next row
+        const int slot_n = d1.x & 0xFFFF;
         double en[NPL];
         ss_emission<NPL, false, ALLLDS>(a, sE, slot_n, lane, en);
         if (hyb && span > a.hyb_th) {
@@ -1055,16 +1086,16 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
     if (lane == 0) a.changed_b[pass] = 1;
     SsBwdC<NPL> cst;
     ss_load_bwd<NPL>(a, lane, cst);
-    const int2 *rd = a.rowdesc + ch.base + rend;                // descriptor of iteration j (row ell = rend - j) is rd[-j]
+    SsDescStream rd = ss_desc_stream(a.rowdesc + ch.base + rend);   // the walk's first descriptor: iteration j is row ell = rend - j
     const int nrows = rend - ch.r0;
-    int2 dcur = rd[-lane], dnxt = rd[-64 - lane];
-    ss_desc_settle(dcur); ss_desc_settle(dnxt);
+    ss_desc_t d1, d2;
+    ss_desc_first<-1>(rd, d1, d2);
     double *brow = a.beta + (size_t)(ch.base + rend) * Mp;      // row ell of iteration j is brow - j Mp
     double *bp[NPL];                                            // MIX: the same address, stepped by -Mp per iteration
 #pragma unroll
     for (int k = 0; k < NPL; ++k) bp[k] = brow + st[k];
     double e[NPL];
-    ss_emission<NPL, true, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    ss_emission<NPL, true, ALLLDS>(a, sE, d1.x & 0xFFFF, lane, e);
     constexpr bool hyb = HYB && NPL == 1;
     const double *tab = sE + (size_t)a.nlds * MS;
     SsEigC ec;
@@ -1080,12 +1111,12 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
     long long npos = 0;
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
-        const int jl = j & 63;
-        const int span = __builtin_amdgcn_readlane(dcur.y, jl);
-        const int ekr = (__builtin_amdgcn_readlane(dcur.x, jl) >> 16) & 0xFF;
+        const ss_desc_t d0 = d1;
+        d1 = d2; d2 = ss_desc_fetch<-1>(rd, d1.x);
+        const int span = d0.y;
+        const int ekr = (d0.x >> 16) & 0xFF;
         npos += span;
-        if (jl == 63) { dcur = dnxt; dnxt = rd[-(j + 65) - lane]; ss_desc_settle(dnxt); }
-        const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
+        const int slot_n = d1.x & 0xFFFF;
         double en[NPL];
         ss_emission<NPL, true, ALLLDS>(a, sE, slot_n, lane, en);
         // beta[ell] in the running scale (hmm.cpp:142 renormalises; every consumer is invariant to a per-row scale)
@@ -1346,22 +1377,22 @@ __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double 
                                                   float (&x)[NPL]) {
     SsLightC<NPL> cst;
     ss_load_light<NPL, false>(a, lane, cst);
-    const int2 *rd = a.rowdesc + base + first + 1;
+    SsDescStream rd = ss_desc_stream(a.rowdesc + base + first + 1);
     const int nrows = last - first;
-    int2 dcur = rd[lane], dnxt = rd[64 + lane];
-    ss_desc_settle(dcur); ss_desc_settle(dnxt);
+    ss_desc_t d1, d2;
+    ss_desc_first<1>(rd, d1, d2);
     float e[NPL];
-    ss_emission_f<NPL, false, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    ss_emission_f<NPL, false, ALLLDS>(a, sE, d1.x & 0xFFFF, lane, e);
     SsJumpR jr;
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<false>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
-        const int jl = j & 63;
-        const int span = __builtin_amdgcn_readlane(dcur.y, jl);
-        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
-        if (jl == 63) { dcur = dnxt; dnxt = rd[j + 65 + lane]; ss_desc_settle(dnxt); }
-        const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
+        const ss_desc_t d0 = d1;
+        d1 = d2; d2 = ss_desc_fetch<1>(rd, d1.x);
+        const int span = d0.y;
+        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
+        const int slot_n = d1.x & 0xFFFF;
         float en[NPL], y[NPL], S;
         ss_emission_f<NPL, false, ALLLDS>(a, sE, slot_n, lane, en);
         ss_fwd_step_f<NPL>(cst, x, e, y, S);
@@ -1394,22 +1425,22 @@ __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double 
                                                   float (&b)[NPL]) {
     SsLightC<NPL> cst;
     ss_load_light<NPL, true>(a, lane, cst);
-    const int2 *rd = a.rowdesc + base + rhi;
+    SsDescStream rd = ss_desc_stream(a.rowdesc + base + rhi);
     const int nrows = rhi - rlo;
-    int2 dcur = rd[-lane], dnxt = rd[-64 - lane];
-    ss_desc_settle(dcur); ss_desc_settle(dnxt);
+    ss_desc_t d1, d2;
+    ss_desc_first<-1>(rd, d1, d2);
     float e[NPL];
-    ss_emission_f<NPL, true, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    ss_emission_f<NPL, true, ALLLDS>(a, sE, d1.x & 0xFFFF, lane, e);
     SsJumpR jr;
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<true>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
-        const int jl = j & 63;
-        const int span = __builtin_amdgcn_readlane(dcur.y, jl);
-        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
-        if (jl == 63) { dcur = dnxt; dnxt = rd[-(j + 65) - lane]; ss_desc_settle(dnxt); }
-        const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
+        const ss_desc_t d0 = d1;
+        d1 = d2; d2 = ss_desc_fetch<-1>(rd, d1.x);
+        const int span = d0.y;
+        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
+        const int slot_n = d1.x & 0xFFFF;
         float en[NPL], y[NPL], Sw;
         ss_emission_f<NPL, true, ALLLDS>(a, sE, slot_n, lane, en);
         ss_bwd_step_f<NPL>(cst, b, e, y, Sw);
@@ -1455,22 +1486,22 @@ __device__ __forceinline__ void ss_forward_light(const SsArgs &a, const double *
     if (lane == 0) { a.changed_f[pass] = 1; a.endchg_f[pass] = 1; }
     SsLightC<NPL> cst;
     ss_load_light<NPL, false>(a, lane, cst);
-    const int2 *rd = a.rowdesc + ch.base + ch.r0 + 1;
+    SsDescStream rd = ss_desc_stream(a.rowdesc + ch.base + ch.r0 + 1);
     const int nrows = ch.r1 - ch.r0;
-    int2 dcur = rd[lane], dnxt = rd[64 + lane];
-    ss_desc_settle(dcur); ss_desc_settle(dnxt);
+    ss_desc_t d1, d2;
+    ss_desc_first<1>(rd, d1, d2);
     float e[NPL];
-    ss_emission_f<NPL, false, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    ss_emission_f<NPL, false, ALLLDS>(a, sE, d1.x & 0xFFFF, lane, e);
     SsJumpR jr;
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<false>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
-        const int jl = j & 63;
-        const int span = __builtin_amdgcn_readlane(dcur.y, jl);
-        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
-        if (jl == 63) { dcur = dnxt; dnxt = rd[j + 65 + lane]; ss_desc_settle(dnxt); }
-        const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
+        const ss_desc_t d0 = d1;
+        d1 = d2; d2 = ss_desc_fetch<1>(rd, d1.x);
+        const int span = d0.y;
+        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
+        const int slot_n = d1.x & 0xFFFF;
         float en[NPL], y[NPL], S;
         ss_emission_f<NPL, false, ALLLDS>(a, sE, slot_n, lane, en);
         ss_fwd_step_f<NPL, H32>(cst, x, e, y, S);
@@ -1527,22 +1558,22 @@ __device__ __forceinline__ void ss_backward_light(const SsArgs &a, const double 
     if (lane == 0) { a.changed_b[pass] = 1; a.endchg_b[pass] = 1; }
     SsLightC<NPL> cst;
     ss_load_light<NPL, true>(a, lane, cst);
-    const int2 *rd = a.rowdesc + ch.base + ch.r1;
+    SsDescStream rd = ss_desc_stream(a.rowdesc + ch.base + ch.r1);
     const int nrows = ch.r1 - ch.r0;
-    int2 dcur = rd[-lane], dnxt = rd[-64 - lane];
-    ss_desc_settle(dcur); ss_desc_settle(dnxt);
+    ss_desc_t d1, d2;
+    ss_desc_first<-1>(rd, d1, d2);
     float e[NPL];
-    ss_emission_f<NPL, true, ALLLDS>(a, sE, __builtin_amdgcn_readlane(dcur.x, 0) & 0xFFFF, lane, e);
+    ss_emission_f<NPL, true, ALLLDS>(a, sE, d1.x & 0xFFFF, lane, e);
     SsJumpR jr;
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<true>(a, lane, jr);
     ss_vm_drain();
     for (int j = 0; j < nrows; ++j) {
-        const int jl = j & 63;
-        const int span = __builtin_amdgcn_readlane(dcur.y, jl);
-        const bool jrow = JMP && (__builtin_amdgcn_readlane(dcur.x, jl) & SS_ROW_JUMP);   // wave-uniform; marked rows are the minority
-        if (jl == 63) { dcur = dnxt; dnxt = rd[-(j + 65) - lane]; ss_desc_settle(dnxt); }
-        const int slot_n = __builtin_amdgcn_readlane(dcur.x, (j + 1) & 63) & 0xFFFF;
+        const ss_desc_t d0 = d1;
+        d1 = d2; d2 = ss_desc_fetch<-1>(rd, d1.x);
+        const int span = d0.y;
+        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
+        const int slot_n = d1.x & 0xFFFF;
         float en[NPL], y[NPL], Sw;
         ss_emission_f<NPL, true, ALLLDS>(a, sE, slot_n, lane, en);
         ss_bwd_step_f<NPL, H32>(cst, b, e, y, Sw);

@@ -1246,7 +1246,8 @@ void smcpp_im::alloc_device() {
     }
     {
         // scan chains: descriptors {key slot, span}; slot = frequency rank of the key (the emission vectors of the first
-        // ss_nlds slots live in LDS); same padding as above with span-1 rows of slot 0
+        // ss_nlds slots live in LDS); same padding as above with span-1 rows of slot 0 (the scan chains request one descriptor per
+        // row, two rows ahead: they read two rows past either end of a contig and consume none of them)
         std::vector<long long> kc(K, 0);
         for (int c = 0; c < n_contigs; ++c)
             for (int i = 1; i <= Ls[c]; ++i) kc[rowinfo[(size_t)contig_base[c] + i].kid]++;
