@@ -176,6 +176,17 @@ int smcpp_last_timing(smcpp_im *im, double out[9]);
  * the longest chunk as short as the slot count allows (the reference parallelises over contigs only, inference_manager.cpp:89-94;
  * this is the engine's own decomposition, exported for the CPU tests). */
 int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *rows, long long nslots, long long floor_cost, int *out);
+/* Host-only (no device needed, none touched): the plan of the chain phase a manager built from these arguments (n[p], na[p]: sample
+ * sizes and distinguished lineages of the npop populations, as smcpp_create_onepop / _twopop take them) would resolve on a device
+ * of `compute_units` compute units after smcpp_set_chunking(rows_per_chunk) (0: automatic), and the chunk lists it would cut.
+ * Runs the host half of the construction - keys, rows, groups, the cut of long rows - and the same resolve and cut functions a
+ * manager runs.  json (up to json_cap - 1 characters): {"plan": {..., "power_jumps": {...}}} as smcpp_describe prints it, with the
+ * per-E-step entries ("light_passes_*", "halo_pass", "float_scans_in_stored_passes", "passes_launched", "power_jumps.run") as a first
+ * E-step on a transition matrix of the reference's structure sets them.  chunks_fwd / chunks_bwd: up to chunk_cap chunks each in
+ * smcpp_debug_chunks' five-int format.  lengths[3]: what the text and the two lists need (call with the caps 0 to size them). */
+int smcpp_host_chain_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs,
+                          int n_hs, const double *hs, int compute_units, int rows_per_chunk,
+                          char *json, int json_cap, int *chunks_fwd, int *chunks_bwd, int chunk_cap, int *lengths);
 int smcpp_chain_mode(smcpp_im *im);
 /* diagnostics (host only): the chunk list of the scan chains as the last plan cut it - backward == 0: the forward chain's, else the
  * backward chain's (the two directions have lists of their own).  Writes up to `cap` chunks into out[5 * cap] as (contig, r0, r1, h0,

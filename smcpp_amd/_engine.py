@@ -76,6 +76,27 @@ def host_chunk_counts(cost, rows, nslots, floor_cost=1):
     return out
 
 
+def host_chain_plan(n, na, contigs, hs, compute_units, rows_per_chunk=0):
+    """The chain plan a manager of these contigs would resolve on a device of `compute_units` compute units, without a device
+    (`smcpp_host_chain_plan`): -> (describe()-style dict with "plan", forward chunks [nf, 5], backward chunks [nb, 5]).
+    n / na: one entry per population (sample size, distinguished lineages)."""
+    import json
+    n = np.ascontiguousarray(np.atleast_1d(n), dtype=np.int32)
+    na = np.ascontiguousarray(np.atleast_1d(na), dtype=np.int32)
+    obs = [np.ascontiguousarray(c, dtype=np.int32) for c in contigs]
+    Ls = np.array([c.shape[0] for c in obs], dtype=np.int32)
+    ptrs = (_ip * len(obs))(*[iptr(c) for c in obs])
+    hs = np.ascontiguousarray(hs, dtype=np.float64)
+    head = (len(n), iptr(n), iptr(na), len(obs), iptr(Ls), ptrs, len(hs), dptr(hs), int(compute_units), int(rows_per_chunk))
+    need = np.zeros(3, dtype=np.int32)
+    check(lib().smcpp_host_chain_plan(*head, None, 0, None, None, 0, iptr(need)))
+    buf = C.create_string_buffer(int(need[0]) + 1)
+    cap = int(max(need[1], need[2], 1))
+    fwd = np.zeros((cap, 5), dtype=np.int32); bwd = np.zeros((cap, 5), dtype=np.int32)
+    check(lib().smcpp_host_chain_plan(*head, buf, int(need[0]) + 1, iptr(fwd), iptr(bwd), cap, iptr(need)))
+    return json.loads(buf.value.decode()), fwd[:need[1]], bwd[:need[2]]
+
+
 def host_eigensystem(A):
     A = np.ascontiguousarray(A, dtype=np.float64)
     n = A.shape[0]

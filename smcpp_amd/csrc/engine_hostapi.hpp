@@ -349,4 +349,41 @@ int smcpp_host_prep_twopop(int n1, int n2, int a1, int a2, int n_hs, const doubl
     API_END
 }
 
+int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *rows, long long nslots, long long floor_cost, int *out) {
+    API_BEGIN
+    if (n_contigs <= 0 || nslots <= 0) throw std::runtime_error("smcpp_host_chunk_counts: empty input");
+    const std::vector<long long> c(cost, cost + n_contigs);
+    const std::vector<int> r(rows, rows + n_contigs);
+    const std::vector<int> ncs = ss_chunk_counts(c, r, nslots, floor_cost);
+    std::copy(ncs.begin(), ncs.end(), out);
+    API_END
+}
+
+// The chain plan of a manager that exists on the host only: build_layout, then the resolve and cut functions every manager runs,
+// then the per-E-step resolve of a first E-step (no warm start, no history).  No stream, no device call.
+int smcpp_host_chain_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs,
+                          int n_hs, const double *hs, int compute_units, int rows_per_chunk,
+                          char *json, int json_cap, int *chunks_fwd, int *chunks_bwd, int chunk_cap, int *lengths) {
+    API_BEGIN
+    if (npop < 1 || npop > 2 || compute_units <= 0) throw std::runtime_error("smcpp_host_chain_plan: one or two populations, at least one compute unit");
+    smcpp_im im;
+    im.build_layout(npop, n, na, n_contigs, Ls, obs, n_hs, hs, 0.5);
+    im.cu_count = compute_units;
+    im.user_rows_per_chunk = rows_per_chunk;
+    im.make_chunks();
+    if (im.plan.scan) {
+        im.chain_pass = im.resolve_chain_pass();
+        im.ss_launched = im.chain_pass.want;
+    }
+    const std::string s = "{" + describe_chain_plan(&im).substr(2) + "}";       // (describe's text starts with ", ")
+    if (json && json_cap > 0) {
+        const size_t k = std::min(s.size(), (size_t)json_cap - 1);
+        std::memcpy(json, s.data(), k);
+        json[k] = 0;
+    }
+    const int nf = smcpp_debug_chunks(&im, 0, chunk_cap, chunks_fwd), nb = smcpp_debug_chunks(&im, 1, chunk_cap, chunks_bwd);
+    if (lengths) { lengths[0] = (int)s.size(); lengths[1] = nf; lengths[2] = nb; }
+    API_END
+}
+
 }  // extern "C"

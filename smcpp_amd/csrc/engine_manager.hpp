@@ -22,6 +22,64 @@ struct StatsPlan {
     bool fin_signals = false;              // the finalisation may raise the completion word itself
 };
 
+// How the chain phase is arranged for one manager and one chunking, resolved from the host layout, the switches and the device's
+// compute-unit count (smcpp_im::resolve_chain_plan - no device call); cut_chunks() cuts the two chunk lists from it, the launches
+// only read it, smcpp_describe() and smcpp_host_chain_plan() print it.  DESIGN.md section 5: field, decided from, switch.
+struct ChainPlan {
+    // the dense fallback family, by the value smcpp_chain_mode() reports: CU-cooperative (one workgroup per chunk, chains2.hpp),
+    // CU-cooperative with streamed operands (64 < M <= 256), lock-step on the matrix cores (16 chunks per workgroup, chains_lock.hpp)
+    enum Dense { COOPERATIVE = 2, STREAMED_OPERANDS = 3, LOCK_STEP = 4 };
+    // hybrid scan chains (un-binned data): rows whose span exceeds hyb_th take ONE eigen-power step inside the scan kernel.  All four
+    // eigenvector tables of every eigen key in LDS; single-direction workgroups with the two tables a direction needs (M > 32); the
+    // same with only the most frequent keys' tables in LDS, the rest - COLD keys - read from L2 (three or four eigen keys)
+    enum Hybrid { NONE, ALL_TABLES, DIRECTION_SPLIT, DIRECTION_SPLIT_COLD_KEYS };
+    bool resolved = false;
+    Dense dense = COOPERATIVE;
+    bool scan = false;                     // the input takes the scan chains (chains_ss.hpp); whether T does is decided on every E-step
+    Hybrid hybrid = NONE;
+    int hyb_th = 0x7fffffff, nk_lds = 0, ekey_of_slot[4] = {0, 1, 2, 3}, eslot_of_key[4] = {0, 1, 2, 3};
+    bool dirsplit() const { return hybrid == DIRECTION_SPLIT || hybrid == DIRECTION_SPLIT_COLD_KEYS; }
+    // launch shape
+    int coop_bpc = 1;                      // cooperative workgroups resident per CU the automatic chunking aims at
+    int wpc = 1;                           // scan chains: wavefronts per SIMD (workgroups per CU) the chunk lists are cut for
+    int wg_waves = 4;                      // wavefronts per workgroup of k_chain_ss (hybrid with two per SIMD: 8, one table copy)
+    bool mid = false;                      // one state per lane, 1.35 - 12 million positions: float halo instead of light passes
+    int nlds = 0;                          // key slots whose emission vectors live in LDS
+    bool all_keys_in_lds = true, two_row_scans = false;        // the instantiation of k_chain_ss
+    // halo pass: the first pass of the scan chains walks into every chunk from a halo (float, then fp64 positions per direction)
+    bool halo = false;
+    long long halo_lf = 0, halo_df = 0, halo_lb = 0, halo_db = 0;
+    // chunking
+    bool by_positions = false;             // the cutter: by positions with halos (scan chains, automatic) or by rows
+    long long positions = 0;               // cost units of all rows (= positions unless hybrid rows are charged SS_HYB_COST)
+    double fwd_share = 0.5;
+    long long waves_fwd = 0, waves_bwd = 0;
+    int rows_per_chunk = 0;                // by rows: rows per chunk
+    std::vector<int> chunks_fwd, chunks_bwd;                   // chunks per contig of either list
+    int max_chunks_per_contig = 1, max_pass = 0;
+    // power jumps of the scan chains (chains_ss.hpp); jump_P = 0: never.  Per manager: a re-plan keeps them
+    int jump_kid = -1, jump_P = 0;
+    // eigen-free pre-pass of the dense families (chains2.hpp: k_group_powers, POWER instantiations)
+    bool power_ok = false;
+    int max_span_pw = 0, pw_nbits = 5, pw_npow = 4;
+};
+
+// What an E-step decides on top of the plan (smcpp_im::resolve_chain_pass): from the chunk counts, the warm start, what the
+// previous E-steps learned (last_ss_passes, ss_need_cert_pass, last_fwd_passes / last_bwd_passes) and the per-E-step switches.
+struct ChainPass {
+    // scan chains
+    bool mixed = false;                    // the scans of the stored passes in float
+    int light_f = 0, light_b = 0;          // light (float, store-free) passes per direction before the full fp64 pass
+    bool use_halo = false;
+    int pass0 = 0;                         // a warm start numbers its passes from 1 or 2: the parity the first pass reads
+    bool jump = false;                     // the launches jump
+    bool cert_up_front = false;            // the all-skip certificate pass is launched with the others
+    int want = 0;                          // passes launched up front
+    // dense families
+    bool dual = false, warm = false, coop_tab = true;
+    int want_f = 0, want_b = 0, prio = 1, prio_mask = 7;
+};
+
 struct smcpp_im {
     // ---- static problem description -------------------------------------------------------------------------
     int npop = 1, keylen = 3, M = 0, Mp = 0, NPL = 1, NT = 1, n_contigs = 0, K = 0, G = 0, Ke = 0;
@@ -110,10 +168,13 @@ struct smcpp_im {
     DevBuf<long long> d_dbg;
     DevBuf<float> d_qTf;
     DevBuf<double> d_qTdT, d_qPinvT, d_qPT, d_qPrm, d_qPinvrm;   // quarter-interleaved operands of the big-M chains
-    int chain_mode = 2;   // dense fallback family: 2 CU-cooperative (one workgroup per chunk, chains2.hpp),
-                          // 3 CU-cooperative with streamed operands (64 < M <= 256), 4 lock-step on the matrix cores (16 chunks per workgroup)
-    int coop_bpc = 1;     // cooperative workgroups resident per CU the automatic chunking aims at
-    // ---- chains on the semiseparable structure of T (chains_ss.hpp; chain_mode 5) ------------------------------------------
+    int cu_count = 0;                      // compute units of the device (build_device), the one device fact the plan uses
+    ChainPlan plan;                        // of this manager and chunking (make_chunks)
+    ChainPass chain_pass;                  // of the last E-step on the scan chains (ss_launch_initial)
+    ChainPlan resolve_chain_plan(int compute_units, const ChainPlan *previous) const;
+    ChainPass resolve_chain_pass() const;
+    void cut_chunks(const ChainPlan &p);
+    // ---- chains on the semiseparable structure of T (chains_ss.hpp; chain family 5) -----------------------------------------
     std::unique_ptr<smcpp_host::OnePopPrep> prep1;   // one-population cold preparation (caches per-key tables)
     std::vector<double> prep1_hs;
     // device cold preparation (prep_dev.hpp): the emission table of the current parameters lives on the device only and the host
@@ -155,54 +216,37 @@ struct smcpp_im {
     enum { Q_ROUTE_NONE = 0, Q_ROUTE_DEVICE, Q_ROUTE_HOST };
     int q_route = Q_ROUTE_NONE;            // who evaluated the last smcpp_q (smcpp_describe: "q_route")
     void ensure_dT();
-    bool ss_static = false;                // the input qualifies (short spans); whether T does is decided on every E-step
-    // hybrid scan chains (un-binned data): rows whose span exceeds ss_hyb_th take ONE eigen-power step inside the scan kernel
-    // (chains_ss.hpp); they cost about SS_HYB_COST scan positions each, which is what the chunk list is balanced on
-    bool ss_hybrid = false;
-    bool ss_halo = false;                  // the first pass of the scan chains walks into every chunk from a halo (make_chunks)
-    int ss_hyb_th = 0x7fffffff;
+    // hybrid rows cost about SS_HYB_COST scan positions each, which is what the chunk list is balanced on
     static constexpr int SS_HYB_COST = 8;
-    long long ss_row_cost(int span) const { return (ss_hybrid && span > ss_hyb_th) ? SS_HYB_COST : span; }
+    static long long ss_row_cost(const ChainPlan &p, int span) { return (p.hybrid && span > p.hyb_th) ? SS_HYB_COST : span; }
     // Power jumps of the scan chains (chains_ss.hpp): in the history passes, every P scan steps inside a row of ONE key become one
-    // mat-vec by the P-th power of that key's operator.  pick_jump_key() decides key and power once per manager; ss_jump_P = 0: never.
-    bool ss_jump_decided = false;
-    int ss_jump_kid = -1, ss_jump_P = 0;
-    bool ss_jump_launch = false;           // the last E-step's launches jumped
-    // what pick_jump_key() charges a jump when it asks whether jumps remove 5 % of the chain work: 3 permlane swaps + 64 fused
+    // mat-vec by the P-th power of that key's operator.  resolve_chain_plan() decides key and power once per manager.
+    // What it charges a jump when it asks whether jumps remove 5 % of the chain work: 3 permlane swaps + 64 fused
     // multiply-adds + 4 adds against the 25 (forward) / 38 (backward) instructions of a light-pass position.  Instruction counts,
     // not a measurement; nothing else reads it (chunks are cut by positions).
     static constexpr int SS_JUMP_COST = 3;
-    bool ss_jump_on() const { return ss_jump_P != 0 && ss_static && !ss_hybrid && NPL == 1; }
+    bool ss_jump_on() const { return plan.jump_P != 0 && plan.scan && !plan.hybrid && NPL == 1; }
     // cost of a row in scan positions with the jumps taken: the first position, the jumps, the scan steps that remain
-    long long ss_jump_cost(int span, int P) const { const long long r = span - 1; return 1 + (r / P) * SS_JUMP_COST + r % P; }
+    static long long ss_jump_cost(int span, int P) { const long long r = span - 1; return 1 + (r / P) * SS_JUMP_COST + r % P; }
     // (the chunk lists stay cut by POSITIONS, jumps or not: seams, halos and every count of the plan are where they were - what
     // tests/test_gpu_seams.py places its features on)
-    void pick_jump_key();
     DevBuf<float> d_jtab_f;                // [2][64][64] off-diagonal part of the power table and its transpose, rebuilt on every E-step
     DevBuf<double> d_jdiag;                // [64] its diagonal
-    bool ss_dirsplit = false;              // hybrid rows at M > 32: single-direction workgroups with two tables per eigen key (chains_ss.hpp)
-    // eigen keys whose tables the hybrid rows keep in LDS (all of them unless they do not fit: then the most frequent ones, the
-    // rest - COLD keys - read their table rows from L2; M > 32 with three or four eigen keys)
-    int ss_nk_lds = 0, ss_ekey_of_slot[4] = {0, 1, 2, 3}, ss_eslot_of_key[4] = {0, 1, 2, 3};
-    size_t ss_tab_bytes() const { return ss_hybrid ? ((size_t)ss_nk_lds * (ss_dirsplit ? 2 : 4) * Mp * (Mp + 1) + 8 * 64) * sizeof(double) : 0; }   // + one scratch vector per wavefront
+    // LDS the hybrid rows' eigenvector tables take (+ one scratch vector per wavefront)
+    static size_t ss_tab_bytes(const ChainPlan &p, int Mp) { return p.hybrid ? ((size_t)p.nk_lds * (p.dirsplit() ? 2 : 4) * Mp * (Mp + 1) + 8 * 64) * sizeof(double) : 0; }
     bool ss_active = false;                // this E-step's chains run on the scan kernels
     bool eigfree = false;                  // ... and its statistics need no eigensystem either (k_span_fold): no eigensolve at all
-    int ss_max_span = 0;
-    int ss_nlds = 0;                       // key slots whose emission vectors live in LDS
-    int ss_wpc = 1;                        // scan chains: wavefronts per SIMD (workgroups per CU) the chunk list is cut for
-    bool ss_mid = false;                   // one state per lane, 1.35 - 12 million positions: float halo instead of light passes, from 1.95 million on with two wavefronts per SIMD (make_chunks)
-    int ss_wg_waves = 4;                   // wavefronts per workgroup of k_chain_ss (hybrid with two per SIMD: 8, one table copy)
+    int ss_max_span = 0;                   // the longest row (build_layout)
+    // what run_chains_ss learns (state, not plan)
     int ss_launched = 0, last_ss_passes = 0;
     bool ss_need_cert_pass = false;     // this input's last working pass rewrites end vectors within tolerance: launch the all-skip pass up front
-    long long ss_positions = 0;            // sum of spans
-    int ss_light_f = 0, ss_light_b = 0;    // light (float, store-free) passes per direction before the full fp64 pass
     // opt-in warm start of the scan chains (smcpp_set_warm_start): the first pass of an E-step starts every chunk from the boundary
     // vector the PREVIOUS converged E-step left (parity ss_warm_parity of the end-vector arrays) instead of pi / the uniform
-    // vector, and one light pass fewer runs; pass indices then start at ss_pass0 (1 or 2: the parity the first pass reads)
+    // vector, and one light pass fewer runs; pass indices then start at ChainPass::pass0 (1 or 2: the parity the first pass reads)
     bool ss_warm_valid = false;
     // lean E-steps copy the (small) parameter arena on stream2 while the chains run; the statistics wait for EV_ARENA
     bool arena_side = false;
-    int ss_warm_parity = 0, ss_pass0 = 0;
+    int ss_warm_parity = 0;
     std::vector<int> ss_slot_of_key;       // frequency rank of every key (slot 0 = most rows)
     DevBuf<int2> d_rowdesc_ss;             // [rows, padded] {key slot, span}
     // rows of binned data longer than 64 positions, cut into pieces at construction (build()): the caller's row counts, the pieces'
@@ -335,8 +379,8 @@ struct smcpp_im {
     int hot_eig = -1, hot_eig2 = -1;
     // eigen-free pre-pass (chains2.hpp: k_group_powers, POWER instantiations): pass 0 runs on group powers while the host
     // solves the eigenproblems; only for short, few spans (binned data) and chunks short enough that pass 1 re-runs them whole
-    bool power_ok = false, prepass_launched = false;
-    int max_span_pw = 0, pw_nbits = 5, pw_npow = 4;
+    // (ChainPlan::power_ok)
+    bool prepass_launched = false;
     PinnedArena pre_stage;                 // static operands of the pre-pass (pi, T, emission table): own pinned mirror
     char *d_pre = nullptr;
     size_t pre_cap = 0;
@@ -393,7 +437,6 @@ struct smcpp_im {
     int ZS = 8;
     int ZG = 1;                          // shares of the per-key gamma-sum reduction of the one-pass span-1 form (a hot key holds most slabs)
     int slab_rows_1 = 0, slab_rows_e = 0;   // rows per span-1 rank slab / per span > 1 slab as make_slabs cut them (smcpp_describe)
-    int max_pass = 0;
     int last_fwd_passes = 0, last_bwd_passes = 0;
     float eps_f = 2e-6f;
     double eps_b = 1e-6;   // relative; beta only enters products with the float alpha (noise floor 2e-6), see DESIGN.md §3
@@ -432,13 +475,18 @@ struct smcpp_im {
 
     void build(int npop_, const int *nn, const int *nna, int n_contigs_, const int *Ls_, const int *const *obs,
                int n_hs, const double *hs_, double pol, int dev);
-    void make_chunks();
+    // its two halves: the host layout (keys, rows, groups, the cut of long rows; no device call) and the device part
+    void build_layout(int npop_, const int *nn, const int *nna, int n_contigs_, const int *Ls_, const int *const *obs,
+                      int n_hs, const double *hs_, double pol);
+    void build_device(int dev);
+    // the plan of this chunking (user_rows_per_chunk) and its chunk lists; a re-plan (smcpp_set_chunking) keeps what is per manager
+    void make_chunks() { plan = resolve_chain_plan(cu_count, plan.resolved ? &plan : nullptr); cut_chunks(plan); }
     void make_slabs();
     void alloc_device();
     void host_prep_and_upload();
     void stage_static_and_prepass();
     void setup_power();
-    ChainArgs chain_args();
+    ChainArgs chain_args(const ChainPass &cp);
     void run_chains();
     void run_stats();            // = enqueue_stats() unless run_chains() already queued them, + finish_stats()
     // signal_epoch != 0: nothing follows on the main stream, and the statistics may raise the completion word with this epoch
@@ -469,6 +517,12 @@ struct smcpp_im {
 // ---------------------------------------------------------------------------------------------------------------
 void smcpp_im::build(int npop_, const int *nn, const int *nna, int n_contigs_, const int *Ls_,
                      const int *const *obs, int n_hs, const double *hs_, double pol, int dev) {
+    build_layout(npop_, nn, nna, n_contigs_, Ls_, obs, n_hs, hs_, pol);
+    build_device(dev);
+}
+
+void smcpp_im::build_layout(int npop_, const int *nn, const int *nna, int n_contigs_, const int *Ls_,
+                            const int *const *obs, int n_hs, const double *hs_, double pol) {
     npop = npop_;
     keylen = 3 * npop;
     for (int p = 0; p < npop; ++p) { n[p] = nn[p]; na[p] = nna[p]; }
@@ -625,7 +679,23 @@ void smcpp_im::build(int npop_, const int *nn, const int *nna, int n_contigs_, c
             const size_t g = (size_t)contig_base[c] + i;
             if (span_of[g] > 1) rowinfo[g].gid = gmap[std::make_pair(rowinfo[g].kid, span_of[g])];
         }
-    // device
+    ss_max_span = 1;
+    for (const Group &g : groups) ss_max_span = std::max(ss_max_span, g.span);
+    {
+        // key slots of the scan chains: slot = frequency rank of the key (slot 0 = most rows; the emission vectors of the first
+        // ChainPlan::nlds slots live in LDS)
+        std::vector<long long> kc(K, 0);
+        for (int c = 0; c < n_contigs; ++c)
+            for (int i = 1; i <= Ls[c]; ++i) kc[rowinfo[(size_t)contig_base[c] + i].kid]++;
+        std::vector<int> order(K);
+        for (int k = 0; k < K; ++k) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return kc[x] > kc[y]; });
+        ss_slot_of_key.assign(K, 0);
+        for (int r = 0; r < K; ++r) ss_slot_of_key[order[r]] = r;
+    }
+}
+
+void smcpp_im::build_device(int dev) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         throw std::runtime_error("no HIP device available: the SMC++ MI355X engine has no CPU fallback");
@@ -649,6 +719,11 @@ void smcpp_im::build(int npop_, const int *nn, const int *nna, int n_contigs_, c
         const unsigned evf = (unsigned)opt().ll(smcpp_opt::O_EVENT_FLAGS, (long long)hipEventDisableSystemFence);
         for (auto &e : ev) HIPCHK(hipEventCreateWithFlags(&e, evf));
     }
+    {
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, device));
+        cu_count = prop.multiProcessorCount;
+    }
     make_chunks();
     make_slabs();
     alloc_device();
@@ -656,14 +731,6 @@ void smcpp_im::build(int npop_, const int *nn, const int *nna, int n_contigs_, c
     // defaults after construction (_smcpp.pyx:318-320)
     alpha = 1.0; theta = 1e-4; rho = 1e-4;
     loglik.assign(n_contigs, 0.0);
-}
-
-// rows per (CU x 16) from which the lock-step chains win (tools/lock_crossover.py on the whole-genome generator: M = 64 and 48
-// from ~400, M = 32 from ~700; at M = 16 the cooperative kernels are never slower)
-static long long lock_min_rows(int Mp) {
-    const long long v = opt().ll(smcpp_opt::O_LOCK_MIN_ROWS, -1);
-    if (v >= 0) return v;
-    return Mp >= 48 ? 450 : Mp >= 32 ? 800 : (1ll << 40);
 }
 
 // Chunks per contig of the scan chains for `nslots` wavefront slots (cost = positions, or cost units with hybrid rows): start from
@@ -699,13 +766,84 @@ static std::vector<int> ss_chunk_counts(const std::vector<long long> &cpos, cons
     return ncs;
 }
 
-// The jump key of the scan chains and whether the input jumps at all (once per manager; chains_ss.hpp: power jumps).
-// SMCPP_SS_JUMP: 0 = never; 16, 8 or 4 = that power, whatever the size of the input (any other value: 8); unset: power 8 on inputs of
-// at least 200 000 positions.
-void smcpp_im::pick_jump_key() {
-    ss_jump_decided = true;
-    ss_jump_kid = -1; ss_jump_P = 0;
-    if (!ss_static || ss_hybrid || NPL != 1 || opt().off(smcpp_opt::O_SS_JUMP)) return;
+// The plan of the chain phase for `compute_units` compute units and the chunking the caller asked for (user_rows_per_chunk).  Reads the
+// host layout and the switches, writes nothing, calls no HIP function: smcpp_host_chain_plan runs it on a machine without a device.
+// `previous`: the plan this one replaces (smcpp_set_chunking) - what is fixed per manager is taken from it.
+ChainPlan smcpp_im::resolve_chain_plan(int compute_units, const ChainPlan *previous) const {
+    ChainPlan p;
+    p.resolved = true;
+    const int cus = std::max(1, compute_units);
+    {
+        // SMCPP_CHAIN = lock: the lock-step kernels forced (M <= 64); = dense: the cooperative kernels; ss (or unset): see below
+        const char *m = opt().has(smcpp_opt::O_CHAIN) ? opt().str(smcpp_opt::O_CHAIN).c_str() : nullptr;
+        if (m) p.dense = (!strcmp(m, "lock") && Mp <= 64) ? ChainPlan::LOCK_STEP : ChainPlan::COOPERATIVE;
+        // lock-step chains on the matrix cores (chains_lock.hpp): 16 chunks per workgroup, so 16 x more and 16 x shorter
+        // chunks - they pay off when those are still long against the ~900 rows of history every chunk re-runs
+        // (rows per (CU x 16) from which they win - tools/lock_crossover.py on the whole-genome generator: M = 64 and 48 from ~400,
+        // M = 32 from ~700; at M = 16 the cooperative kernels are never slower)
+        const long long lock_min_rows = opt().ll(smcpp_opt::O_LOCK_MIN_ROWS, -1) >= 0 ? opt().ll(smcpp_opt::O_LOCK_MIN_ROWS, -1)
+                                        : Mp >= 48 ? 450 : Mp >= 32 ? 800 : (1ll << 40);
+        if (!m && Mp <= 64 && (total_rows - n_contigs) / ((long long)compute_units * LOCK_NC) >= lock_min_rows) {
+            // ... and when one eigen key dominates the span > 1 rows (binned data: the monomorphic key): only its operators are
+            // register-resident there, every other key present in a step costs two L2 round trips for the whole workgroup
+            std::vector<long long> cnt(std::max(1, Ke), 0);
+            long long ne = 0;
+            for (const RowInfo &ri : rowinfo)
+                if (ri.gid >= 0) { ++cnt[groups[ri.gid].eig]; ++ne; }
+            const long long top = *std::max_element(cnt.begin(), cnt.end());
+            if (ne == 0 || 10 * top >= 9 * ne) p.dense = ChainPlan::LOCK_STEP;
+        }
+        // 64 < M <= 256: the streaming cooperative kernels (k_fwd_big / k_bwd_big)
+        if (Mp > 64) p.dense = ChainPlan::STREAMED_OPERANDS;
+        // Chains on the semiseparable structure of T (chains_ss.hpp): one position per step, so the input qualifies when
+        // its spans are short (binned data; un-binned posterior data with spans of 10^4 .. 10^5 keep the eigen kernels).
+        // `dense` then names the DENSE kernels an E-step falls back to when its T has no such structure.
+        const bool ss_ok = !opt().off(smcpp_opt::O_SS) && (!m || !strcmp(m, "ss")) && Mp <= 1024;
+        p.scan = ss_ok && ss_max_span <= 512;
+        if (ss_ok && !p.scan) {
+            // longer spans: the hybrid form, when one state per lane holds the vector and the eigenvector tables of every eigen
+            // key fit LDS beside the emission vectors (SMCPP_HYBRID=0: the dense kernels)
+            const bool hy_off = opt().off(smcpp_opt::O_HYBRID);
+            const size_t tab = (size_t)Ke * 4 * Mp * (Mp + 1) * sizeof(double);
+            const bool fits = !hy_off && Mp <= 64 && Ke >= 1 && Ke <= 4;
+            if (fits && tab <= 120 * 1024) p.hybrid = ChainPlan::ALL_TABLES;
+            // (round 4) M > 32: four 33 KB tables per eigen key do not fit, the two a DIRECTION needs do - every workgroup
+            // runs one direction (the task table keeps them apart) and stages that direction's pair
+            else if (fits && tab / 2 <= 136 * 1024) p.hybrid = ChainPlan::DIRECTION_SPLIT;
+            // (round 5) ... and with three or four eigen keys at M > 32 not even those: the most frequent keys keep their pair
+            // in LDS, a COLD key's table rows are read from L2 on the rows that need them (chains_ss.hpp: ss_eig_matvec_cold)
+            else if (fits && Mp > 32 && tab / 2 / Ke <= 136 * 1024) p.hybrid = ChainPlan::DIRECTION_SPLIT_COLD_KEYS;
+            if (p.hybrid) { p.scan = true; p.hyb_th = std::max(1, opt().i(smcpp_opt::O_HYB_TH, 6)); }
+            p.nk_lds = Ke;
+            if (p.hybrid == ChainPlan::DIRECTION_SPLIT_COLD_KEYS) {
+                // slots by frequency of the keys' hybrid rows
+                std::vector<long long> cnt(Ke, 0);
+                for (const RowInfo &ri : rowinfo)
+                    if (ri.gid >= 0 && groups[ri.gid].span > p.hyb_th) ++cnt[groups[ri.gid].eig];
+                std::vector<int> order(Ke);
+                for (int e = 0; e < Ke; ++e) order[e] = e;
+                std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cnt[x] > cnt[y]; });
+                p.nk_lds = (int)std::max<size_t>(1, std::min<size_t>((size_t)Ke, (size_t)(136 * 1024) / (tab / 2 / Ke)));
+                for (int e = 0; e < 4; ++e) p.eslot_of_key[e] = -1;
+                for (int sl = 0; sl < p.nk_lds; ++sl) { p.ekey_of_slot[sl] = order[sl]; p.eslot_of_key[order[sl]] = sl; }
+            }
+        }
+        if (p.scan) p.dense = Mp > 64 ? ChainPlan::STREAMED_OPERANDS : ChainPlan::COOPERATIVE;
+        if (opt().i(smcpp_opt::O_COOP_BPC, 0) > 0) p.coop_bpc = opt().i(smcpp_opt::O_COOP_BPC, 0);
+        else {
+            // More workgroups per CU hide the per-row latency of the cooperative kernels (measured on 6.8 M rows:
+            // throughput x1.27 / x1.36 / x1.42 for 2 / 3 / 4 per CU) but shorten the chunks, and every chunk pays
+            // ~1100 rows of re-run history; the break-even points below follow from those two numbers.
+            const long long per_cu = (total_rows - n_contigs) / cus;
+            p.coop_bpc = per_cu < 3000 ? 1 : per_cu < 9000 ? 2 : per_cu < 17000 ? 3 : 4;
+        }
+    }
+    // The jump key of the scan chains and whether the input jumps at all (once per manager: the row descriptors carry it, and it does
+    // not depend on the chunking; chains_ss.hpp: power jumps).  SMCPP_SS_JUMP: 0 = never; 16, 8 or 4 = that power, whatever the size
+    // of the input (any other value: 8); unset: power 8 on inputs of at least 200 000 positions.
+    if (previous) { p.jump_kid = previous->jump_kid; p.jump_P = previous->jump_P; }
+    else [&] {
+    if (!p.scan || p.hybrid || NPL != 1 || opt().off(smcpp_opt::O_SS_JUMP)) return;
     int P = opt().i(smcpp_opt::O_SS_JUMP, 8);
     if (P != 16 && P != 8 && P != 4) P = 8;
     // positions in span > 1 rows per key, all positions
@@ -734,184 +872,52 @@ void smcpp_im::pick_jump_key() {
     // history fed them (scan steps 1.3e-6, jumps by 16 / 4 / 8: 0.3 / 0.7 / 2.3e-6; either is 1.6 .. 2.1e-6 from the reference), and
     // tests/test_gpu_parity.py holds that difference to 2e-6.  DESIGN.md section 6.
     if (!opt().has(smcpp_opt::O_SS_JUMP) && total < 200000) return;
-    ss_jump_kid = best; ss_jump_P = P;
-}
-
-void smcpp_im::make_chunks() {
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    {
-        // SMCPP_CHAIN = lock: the lock-step kernels forced (M <= 64); = dense: the cooperative kernels; ss (or unset): see below
-        const char *m = opt().has(smcpp_opt::O_CHAIN) ? opt().str(smcpp_opt::O_CHAIN).c_str() : nullptr;
-        if (m) chain_mode = (!strcmp(m, "lock") && Mp <= 64) ? 4 : 2;
-        // lock-step chains on the matrix cores (chains_lock.hpp): 16 chunks per workgroup, so 16 x more and 16 x shorter
-        // chunks - they pay off when those are still long against the ~900 rows of history every chunk re-runs
-        if (!m && Mp <= 64 && (total_rows - n_contigs) / ((long long)prop.multiProcessorCount * LOCK_NC) >= lock_min_rows(Mp)) {
-            // ... and when one eigen key dominates the span > 1 rows (binned data: the monomorphic key): only its operators are
-            // register-resident there, every other key present in a step costs two L2 round trips for the whole workgroup
-            std::vector<long long> cnt(std::max(1, Ke), 0);
-            long long ne = 0;
-            for (const RowInfo &ri : rowinfo)
-                if (ri.gid >= 0) { ++cnt[groups[ri.gid].eig]; ++ne; }
-            const long long top = *std::max_element(cnt.begin(), cnt.end());
-            if (ne == 0 || 10 * top >= 9 * ne) chain_mode = 4;
+    p.jump_kid = best; p.jump_P = P;
+    }();
+    // cost units (positions, or SS_HYB_COST for a hybrid row) per contig and in all
+    std::vector<long long> cpos(n_contigs, 0);
+    for (int c = 0; c < n_contigs; ++c) {
+        for (int i = 1; i <= Ls[c]; ++i) {
+            const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+            cpos[c] += ri.gid < 0 ? 1 : ss_row_cost(p, groups[ri.gid].span);
         }
-        // 64 < M <= 256: the streaming cooperative kernels (k_fwd_big / k_bwd_big)
-        if (Mp > 64) chain_mode = 3;
-        // Chains on the semiseparable structure of T (chains_ss.hpp): one position per step, so the input qualifies when
-        // its spans are short (binned data; un-binned posterior data with spans of 10^4 .. 10^5 keep the eigen kernels).
-        // chain_mode then names the DENSE kernels an E-step falls back to when its T has no such structure.
-        ss_max_span = 1;
-        for (const Group &g : groups) ss_max_span = std::max(ss_max_span, g.span);
-        {
-            const bool ss_ok = !opt().off(smcpp_opt::O_SS) && (!m || !strcmp(m, "ss")) && Mp <= 1024;
-            ss_static = ss_ok && ss_max_span <= 512;
-            ss_hybrid = false; ss_hyb_th = 0x7fffffff;
-            if (ss_ok && !ss_static) {
-                // longer spans: the hybrid form, when one state per lane holds the vector and the eigenvector tables of every eigen
-                // key fit LDS beside the emission vectors (SMCPP_HYBRID=0: the dense kernels)
-                const bool hy_off = opt().off(smcpp_opt::O_HYBRID);
-                const int hyb_th_opt = std::max(1, opt().i(smcpp_opt::O_HYB_TH, 6));
-                const size_t tab = (size_t)Ke * 4 * Mp * (Mp + 1) * sizeof(double);
-                ss_dirsplit = false;
-                if (!hy_off && Mp <= 64 && Ke >= 1 && Ke <= 4 && tab <= 120 * 1024) {
-                    ss_static = ss_hybrid = true;
-                    ss_hyb_th = hyb_th_opt;
-                } else if (!hy_off && Mp <= 64 && Ke >= 1 && Ke <= 4 && tab / 2 <= 136 * 1024) {
-                    // (round 4) M > 32: four 33 KB tables per eigen key do not fit, the two a DIRECTION needs do - every workgroup
-                    // runs one direction (the task table keeps them apart) and stages that direction's pair
-                    ss_static = ss_hybrid = ss_dirsplit = true;
-                    ss_hyb_th = hyb_th_opt;
-                } else if (!hy_off && Mp > 32 && Mp <= 64 && Ke >= 1 && Ke <= 4 && tab / 2 / Ke <= 136 * 1024) {
-                    // (round 5) ... and with three or four eigen keys at M > 32 not even those: the most frequent keys keep their pair
-                    // in LDS, a COLD key's table rows are read from L2 on the rows that need them (chains_ss.hpp: ss_eig_matvec_cold)
-                    ss_static = ss_hybrid = ss_dirsplit = true;
-                    ss_hyb_th = hyb_th_opt;
-                }
-                ss_nk_lds = Ke;
-                for (int e = 0; e < 4; ++e) ss_ekey_of_slot[e] = ss_eslot_of_key[e] = e;
-                if (ss_hybrid && ss_dirsplit && tab / 2 > 136 * 1024) {
-                    // slots by frequency of the keys' hybrid rows
-                    std::vector<long long> cnt(Ke, 0);
-                    for (const RowInfo &ri : rowinfo)
-                        if (ri.gid >= 0 && groups[ri.gid].span > ss_hyb_th) ++cnt[groups[ri.gid].eig];
-                    std::vector<int> order(Ke);
-                    for (int e = 0; e < Ke; ++e) order[e] = e;
-                    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cnt[x] > cnt[y]; });
-                    ss_nk_lds = (int)std::max<size_t>(1, std::min<size_t>((size_t)Ke, (size_t)(136 * 1024) / (tab / 2 / Ke)));
-                    for (int e = 0; e < 4; ++e) ss_eslot_of_key[e] = -1;
-                    for (int sl = 0; sl < ss_nk_lds; ++sl) { ss_ekey_of_slot[sl] = order[sl]; ss_eslot_of_key[order[sl]] = sl; }
-                }
-            }
-            if (ss_static) chain_mode = Mp > 64 ? 3 : 2;
-            if (!ss_jump_decided) pick_jump_key();
-        }
-        if (opt().i(smcpp_opt::O_COOP_BPC, 0) > 0) coop_bpc = opt().i(smcpp_opt::O_COOP_BPC, 0);
-        else {
-            // More workgroups per CU hide the per-row latency of the cooperative kernels (measured on 6.8 M rows:
-            // throughput x1.27 / x1.36 / x1.42 for 2 / 3 / 4 per CU) but shorten the chunks, and every chunk pays
-            // ~1100 rows of re-run history; the break-even points below follow from those two numbers.
-            const long long per_cu = (total_rows - n_contigs) / std::max(1, prop.multiProcessorCount);
-            coop_bpc = per_cu < 3000 ? 1 : per_cu < 9000 ? 2 : per_cu < 17000 ? 3 : 4;
-        }
+        p.positions += cpos[c];
     }
-    // chunks in flight: one per SIMD for the per-wavefront kernels, coop_bpc per CU for the cooperative ones
-    long long slots = (long long)prop.multiProcessorCount *
-                      (chain_mode == 4 ? LOCK_NC : chain_mode == 3 ? 1 : coop_bpc);
-    if (ss_static && user_rows_per_chunk <= 0 && !opt().has(smcpp_opt::O_ROWS_PER_CHUNK)) {
+    const long long total_bins = p.positions;
+    if (previous) { p.wpc = previous->wpc; p.wg_waves = previous->wg_waves; p.mid = previous->mid; }   // (the by-rows cutter leaves them as they were)
+    p.by_positions = p.scan && user_rows_per_chunk <= 0 && !opt().has(smcpp_opt::O_ROWS_PER_CHUNK);
+    if (p.by_positions) {
         // scan chains: one wavefront per chunk and direction, a workgroup = 2 forward + 2 backward chunks = one wavefront per
         // SIMD; chunks are cut by POSITIONS (sum of spans), the unit of work of these kernels.  Every chunk pays the same
         // ~3000 positions of re-run history however short it is (the chains forget with an e-fold of ~240 positions).
-        std::vector<long long> cum;
-        long long total_bins = 0;
-        for (int c = 0; c < n_contigs; ++c)
-            for (int i = 1; i <= Ls[c]; ++i) {
-                const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
-                total_bins += ri.gid < 0 ? 1 : ss_row_cost(groups[ri.gid].span);
-            }
         // Wavefronts per SIMD: one wavefront leaves a quarter of the issue slots empty (an instruction occupies the SIMD for 4 of
         // the ~5.3 clocks between two issues of one wavefront), a second and third fill them - but every chunk pays ~3 000 positions
         // of re-run history, so only inputs whose chunks stay long (>= 9 000 positions) take them.  Whole genome (28.7 M
         // positions): 9.3 / 8.2 / 7.9 ms of chains with 1 / 2 / 3; a 3.4 M-position shard: 1.83 / 1.95 ms with 1 / 2.
-        const long long simds = (long long)prop.multiProcessorCount * 4;
+        const long long simds = (long long)compute_units * 4;
         // (round 6, last session) one state per lane, re-measured on single contigs of 150 ... 1 700 Mbp and a rank's shard of the genome
         // (gpurun_out/r06_gp12 ... gp17): between 1.95 and 12 million positions TWO wavefronts per SIMD that enter their chunks through a
         // float halo (no light passes, no fp64 part of the halo) beat one wavefront with light passes by 10 - 19 % (250 Mbp 1.66 -> 1.44 ms,
         // 700 Mbp 2.94 -> 2.46, 1 100 Mbp 4.15 -> 3.37, the 8-GPU run's shard 1.75 -> 1.57), from 12 million on three wavefronts without a
         // halo win (1 700 Mbp 6.01 -> 4.59; whole genome unchanged); below 1.35 million (the headline: 1 million) nothing changes.
-        ss_mid = false;
+        p.mid = false;
         int wpc_auto = (int)std::max<long long>(1, std::min<long long>(3, total_bins / (simds * 9000)));
-        if (NPL == 1 && !ss_hybrid) {
+        if (NPL == 1 && !p.hybrid) {
             const long long per_simd = total_bins / std::max<long long>(1, simds);
             // (... and between 1.35 and 1.95 million the halo with ONE wavefront: 135 / 150 / 175 Mbp 1.19 / 1.34 / 1.52 -> 1.12 / 1.18 / 1.27 ms;
             // at 200 Mbp the light passes hit a sweet spot - 1 + 1 of them, three launches, 1.26 ms - that the halo forms miss by 3 %:
             // the rule stays monotone, gpurun_out/r06_gp17)
             wpc_auto = per_simd >= 11700 ? 3 : per_simd >= 1900 ? 2 : 1;
-            ss_mid = (wpc_auto == 2 || per_simd >= 1300) && wpc_auto < 3 && !opt().has(smcpp_opt::O_SS_WPC);
+            p.mid = (wpc_auto == 2 || per_simd >= 1300) && wpc_auto < 3 && !opt().has(smcpp_opt::O_SS_WPC);
         }
-        ss_wpc = opt().has(smcpp_opt::O_SS_WPC) ? std::max(1, std::min(4, opt().i(smcpp_opt::O_SS_WPC, 1))) : wpc_auto;
+        p.wpc = opt().has(smcpp_opt::O_SS_WPC) ? std::max(1, std::min(4, opt().i(smcpp_opt::O_SS_WPC, 1))) : wpc_auto;
         // hybrid rows are bound by instruction and LDS LATENCY (a dependent chain of ~200 instructions per row): a second wavefront
         // per SIMD fills the gaps from ~2 000 cost units per chunk on (posterior workload: 1.79 -> 1.35 ms of chains; a third one
         // needs an extra pass: 1.80); the eight wavefronts form ONE workgroup so that the CU holds one copy of the tables
-        if (ss_hybrid && !opt().has(smcpp_opt::O_SS_WPC)) ss_wpc = (int)std::max<long long>(1, std::min<long long>(2, total_bins / (simds * 2000)));
-        if (ss_hybrid) ss_wpc = std::min(ss_wpc, 2);
-        ss_wg_waves = (ss_hybrid && ss_wpc == 2) ? 8 : 4;
-        const long long waves = simds * ss_wpc;
-        max_chunks_per_contig = 1;
-        // positions per contig
-        std::vector<long long> cpos(n_contigs, 0);
-        for (int c = 0; c < n_contigs; ++c)
-            for (int i = 1; i <= Ls[c]; ++i) {
-                const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
-                cpos[c] += ri.gid < 0 ? 1 : ss_row_cost(groups[ri.gid].span);
-            }
-        auto cut = [&](long long nslots, long long floor_bins, std::vector<Chunk> &out, bool bwd, long long halo_l, long long halo_d) {
-            // Chunks per contig: NEVER more chunks than wavefront slots in total (a launch of 1046 wavefronts on 1024 SIMDs puts two
-            // on some of them, and the kernel then lasts as long as those take: whole genome, 22 contigs each rounded up, +27 %).
-            // Start from the rounded-down share of every contig and hand the remaining slots, one at a time, to the contig whose
-            // chunks are currently the longest (minimises the longest chunk).
-            const std::vector<int> ncs = ss_chunk_counts(cpos, Ls, nslots, floor_bins);
-            out.clear();
-            for (int c = 0; c < n_contigs; ++c) {
-                const int L = Ls[c];
-                cum.assign((size_t)L + 1, 0);
-                for (int i = 1; i <= L; ++i) {
-                    const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
-                    cum[i] = cum[i - 1] + (ri.gid < 0 ? 1 : ss_row_cost(groups[ri.gid].span));
-                }
-                const int nc = ncs[c];
-                max_chunks_per_contig = std::max(max_chunks_per_contig, nc);
-                int prev = 0;
-                for (int j = 0; j < nc; ++j) {
-                    int r1;
-                    if (j == nc - 1) r1 = L;
-                    else {
-                        const long long target = cum[L] * (j + 1) / nc;
-                        r1 = (int)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
-                        r1 = std::max(prev + 1, std::min(r1, L - (nc - 1 - j)));
-                    }
-                    Chunk ch;
-                    ch.base = contig_base[c];
-                    ch.r0 = prev; ch.r1 = r1; ch.contig = c;
-                    ch.first = (j == 0); ch.last = (j == nc - 1); ch.pad = 0;
-                    // halo rows (positions counted on this contig's cumulative costs): forward chunks look back, backward ones ahead
-                    if (bwd) {
-                        const long long e1 = cum[r1] + halo_d, e0 = e1 + halo_l;
-                        ch.h1 = (int)std::min<long long>(L, std::lower_bound(cum.begin(), cum.end(), e1) - cum.begin());
-                        ch.h0 = (int)std::min<long long>(L, std::lower_bound(cum.begin(), cum.end(), e0) - cum.begin());
-                        if (halo_l + halo_d == 0 || ch.last) ch.h0 = ch.h1 = r1;
-                    } else {
-                        const long long e1 = cum[prev] - halo_d, e0 = e1 - halo_l;
-                        ch.h1 = e1 <= 0 ? 0 : (int)(std::upper_bound(cum.begin(), cum.end(), e1) - cum.begin()) - 1;
-                        ch.h0 = e0 <= 0 ? 0 : (int)(std::upper_bound(cum.begin(), cum.end(), e0) - cum.begin()) - 1;
-                        ch.h1 = std::min(ch.h1, prev); ch.h0 = std::min(ch.h0, ch.h1);
-                        if (halo_l + halo_d == 0 || ch.first) ch.h0 = ch.h1 = prev;
-                    }
-                    out.push_back(ch);
-                    prev = r1;
-                }
-            }
-        };
+        if (p.hybrid && !opt().has(smcpp_opt::O_SS_WPC)) p.wpc = (int)std::max<long long>(1, std::min<long long>(2, total_bins / (simds * 2000)));
+        if (p.hybrid) p.wpc = std::min(p.wpc, 2);
+        p.wg_waves = (p.hybrid && p.wpc == 2) ? 8 : 4;
+        const long long waves = simds * p.wpc;
         // Halo pass (chains_ss.hpp): with several chunks per contig every wavefront first walks into its chunk from its neighbour's
         // rows - `light` positions in float, then `dbl` in fp64, neither stored - so that ONE launch leaves rows that are already
         // exact to the certificate's tolerance (the chains forget with an e-fold of ~240 positions forward, ~340 backward: 11.5 +
@@ -921,10 +927,11 @@ void smcpp_im::make_chunks() {
         // 0.87; with several states per lane (M > 64), where a light position costs relatively more, it wins (c5: 1.45 against 1.64 ms).
         // Default: M > 64 only; SMCPP_SS_HALO = 1 / 0 forces it.
         // (the mid-size regime of one state per lane, above: halo on, float part only)
-        ss_halo = !ss_hybrid && (opt().has(smcpp_opt::O_SS_HALO) ? opt().i(smcpp_opt::O_SS_HALO, 0) != 0 : (NPL >= 2 || ss_mid));
-        const bool mid_halo = ss_halo && ss_mid && NPL == 1;
-        const long long hlf = ss_halo ? opt().ll(smcpp_opt::O_HALO_LF, 2800) : 0, hdf = ss_halo ? opt().ll(smcpp_opt::O_HALO_DF, mid_halo ? 0 : 800) : 0,
-                        hlb = ss_halo ? opt().ll(smcpp_opt::O_HALO_LB, 3900) : 0, hdb = ss_halo ? opt().ll(smcpp_opt::O_HALO_DB, mid_halo ? 0 : 1100) : 0;
+        p.halo = !p.hybrid && (opt().has(smcpp_opt::O_SS_HALO) ? opt().i(smcpp_opt::O_SS_HALO, 0) != 0 : (NPL >= 2 || p.mid));
+        const bool mid_halo = p.halo && p.mid && NPL == 1;
+        const long long hlf = p.halo ? opt().ll(smcpp_opt::O_HALO_LF, 2800) : 0, hdf = p.halo ? opt().ll(smcpp_opt::O_HALO_DF, mid_halo ? 0 : 800) : 0,
+                        hlb = p.halo ? opt().ll(smcpp_opt::O_HALO_LB, 3900) : 0, hdb = p.halo ? opt().ll(smcpp_opt::O_HALO_DB, mid_halo ? 0 : 1100) : 0;
+        p.halo_lf = hlf; p.halo_df = hdf; p.halo_lb = hlb; p.halo_db = hdb;
         {
             // the forward chain gets SMCPP_SS_FWD_SHARE of the wavefronts.  Default one half: the backward chain's light position
             // costs 38 instructions against 25, but the fp64 passes of the two directions take the same time (forward: stores, the
@@ -933,7 +940,7 @@ void smcpp_im::make_chunks() {
             // (halo pass: the backward wavefronts carry the longer halo and the dearer position, so they get more, shorter chunks:
             // per wavefront halo_f + 53 P / c_f = halo_b + 59 P / c_b instructions with c_f + c_b = waves)
             double dflt_share = 0.5;
-            if (ss_halo && total_bins > 0) {
+            if (p.halo && total_bins > 0) {
                 const double Hf = 25.0 * hlf + 53.0 * hdf, Hb = 29.0 * hlb + 59.0 * hdb, P = (double)total_bins, W = (double)waves;
                 double lo = 0.05, hi = 0.95;
                 for (int it = 0; it < 40; ++it) {
@@ -947,46 +954,137 @@ void smcpp_im::make_chunks() {
                 // is the optimum, 0 - 3 % ahead of the balance above, whose per-position costs are those of several states per lane)
                 if (mid_halo) dflt_share = 0.5;
             }
-            const double share = opt().d(smcpp_opt::O_SS_FWD_SHARE, dflt_share);
-            const long long nf = std::max<long long>(1, (long long)(share * (double)waves + 0.5));
-            cut(nf, 1024, chunks, false, hlf, hdf);
-            cut(std::max<long long>(1, waves - nf), 1024, chunks_b, true, hlb, hdb);
+            p.fwd_share = opt().d(smcpp_opt::O_SS_FWD_SHARE, dflt_share);
+            p.waves_fwd = std::max<long long>(1, (long long)(p.fwd_share * (double)waves + 0.5));
+            p.waves_bwd = std::max<long long>(1, waves - p.waves_fwd);
         }
-        max_pass = max_chunks_per_contig + 3 + 4 + 2;  // (+4: light passes, +2: a warm start numbers its passes from 1 or 2)
+        // Chunks per contig: NEVER more chunks than wavefront slots in total (a launch of 1046 wavefronts on 1024 SIMDs puts two
+        // on some of them, and the kernel then lasts as long as those take: whole genome, 22 contigs each rounded up, +27 %).
+        // Start from the rounded-down share of every contig and hand the remaining slots, one at a time, to the contig whose
+        // chunks are currently the longest (minimises the longest chunk).  No chunk below 1 024 positions.
+        p.chunks_fwd = ss_chunk_counts(cpos, Ls, p.waves_fwd, 1024);
+        p.chunks_bwd = ss_chunk_counts(cpos, Ls, p.waves_bwd, 1024);
+    } else {
+        // chunks in flight: one per SIMD for the per-wavefront kernels, coop_bpc per CU for the cooperative ones
+        const long long slots = (long long)compute_units *
+                                (p.dense == ChainPlan::LOCK_STEP ? LOCK_NC : p.dense == ChainPlan::STREAMED_OPERANDS ? 1 : p.coop_bpc);
+        const long long rows = total_rows - n_contigs;
+        int lc = user_rows_per_chunk;
+        if (lc <= 0) lc = opt().i(smcpp_opt::O_ROWS_PER_CHUNK, lc);
+        // every chunk pays ~1000 rows of re-run history however short it is, so small inputs get few, long chunks rather
+        // than one sliver per CU (a 1 500-row contig: 3 chunks and 4 passes instead of 24 chunks and 15 passes)
+        if (lc <= 0) lc = (int)std::max<long long>(512, (rows + slots - 1) / slots);
+        p.rows_per_chunk = lc;
+        p.chunks_fwd.resize(n_contigs);
+        for (int c = 0; c < n_contigs; ++c) p.chunks_fwd[c] = std::max(1, ceil_div(Ls[c], lc));
+        p.chunks_bwd = p.chunks_fwd;             // (the backward list is a copy of the forward one: no halo on this path)
+    }
+    for (int c = 0; c < n_contigs; ++c) p.max_chunks_per_contig = std::max(p.max_chunks_per_contig, std::max(p.chunks_fwd[c], p.chunks_bwd[c]));
+    p.max_pass = p.max_chunks_per_contig + 3;    // (+1: the full pass that follows an eigen-free pre-pass)
+    if (p.scan) p.max_pass += 4 + 2;             // (+4: light passes, +2: a warm start numbers its passes from 1 or 2)
+    // the emission vectors of the first nlds key slots live in LDS; the instantiation of k_chain_ss follows from it: every key slot
+    // in LDS (the usual case) is the one without the global path of the emission vectors, and at M <= 32 with one state per lane
+    // and no hybrid rows its scans skip the level that would only move zeros (SMCPP_SS_H32=0: the full-width form there too)
+    // (fixed at construction; wpc workgroups share a CU's 160 KB, the hybrid form runs one workgroup per CU beside its tables.
+    // Until round 5 the table was capped at 64 KB: the 192 six-int keys of config C4 - 96 KB at M = 48 - left 64 slots to the L2 path
+    // and with them the kernel to its instantiation with vector-memory waits on every row: chains 0.86 -> see DESIGN.md section 6)
+    const long long slot_bytes = 64 * NPL * 8;
+    if (previous) p.nlds = previous->nlds;
+    else if (p.hybrid) p.nlds = (int)std::max<long long>(1, std::min<long long>(K, (long long)((p.dirsplit() ? 158 : 150) * 1024 - ss_tab_bytes(p, Mp)) / slot_bytes));
+    else p.nlds = (int)std::min<long long>(K, ((150 / std::max(1, p.wpc)) * 1024) / slot_bytes);
+    p.all_keys_in_lds = K <= p.nlds;
+    p.two_row_scans = NPL == 1 && !p.hybrid && p.all_keys_in_lds && Mp <= 32 && !opt().off(smcpp_opt::O_SS_H32);
+    {
+        // Eigen-free pre-pass of the dense families: spans below 32 (binned data: four squarings give every power); chunks short
+        // enough that pass 1 re-runs them whole anyway (the rows of the pre-pass are all overwritten: it runs in float and its
+        // normalisers carry no eigenvalue scale)
+        int mx = 0, longest = 0;
+        for (int g = 0; g < G; ++g) mx = std::max(mx, groups[g].span);
+        if (!p.by_positions)
+            for (int c = 0; c < n_contigs; ++c)
+                for (int j = 0, nc = p.chunks_fwd[c]; j < nc; ++j)
+                    longest = std::max(longest, (int)((long long)Ls[c] * (j + 1) / nc) - (int)((long long)Ls[c] * j / nc));
+        const char *pe = opt().has(smcpp_opt::O_POWER_PREPASS) ? opt().str(smcpp_opt::O_POWER_PREPASS).c_str() : nullptr;
+        const bool coop_pre = p.dense == ChainPlan::COOPERATIVE && Mp <= 64;
+        const bool big_pre = p.dense == ChainPlan::STREAMED_OPERANDS && Mp > 64 && Mp <= 256;
+        // spans up to twelve bits (4095 positions); the cooperative chains read the powers beyond A^16 from L2 on the few rows
+        // that need them, the streamed-operand ones stream every power anyway
+        p.power_ok = (coop_pre || big_pre) && mx <= 4095 && Ke >= 1 && G >= 1 && longest <= 2000 && !(pe && atoi(pe) == 0) && !p.scan;
+        p.max_span_pw = mx;
+        while ((1 << p.pw_nbits) <= mx) ++p.pw_nbits;
+        p.pw_npow = p.pw_nbits - 1;
+    }
+    return p;
+}
+
+// The two chunk lists of a plan: by positions with halos (the automatic chunking of the scan chains), or by rows.  Decides nothing.
+void smcpp_im::cut_chunks(const ChainPlan &p) {
+    max_chunks_per_contig = p.max_chunks_per_contig;
+    if (!p.by_positions) {
+        chunks.clear();
+        for (int c = 0; c < n_contigs; ++c) {
+            const int L = Ls[c], nc = p.chunks_fwd[c];
+            for (int j = 0; j < nc; ++j) {
+                Chunk ch;
+                ch.base = contig_base[c];
+                ch.r0 = (int)((long long)L * j / nc);
+                ch.r1 = (int)((long long)L * (j + 1) / nc);
+                ch.contig = c;
+                ch.first = (j == 0);
+                ch.last = (j == nc - 1);
+                ch.pad = 0;
+                ch.h0 = ch.h1 = ch.r0;               // (forward list; the backward copy below is given r1: no halo on this path)
+                chunks.push_back(ch);
+            }
+        }
+        chunks_b = chunks;
+        for (Chunk &cb : chunks_b) cb.h0 = cb.h1 = cb.r1;
         return;
     }
-    long long rows = total_rows - n_contigs;
-    int lc = user_rows_per_chunk;
-    if (lc <= 0) {
-        lc = opt().i(smcpp_opt::O_ROWS_PER_CHUNK, lc);
-    }
-    // every chunk pays ~1000 rows of re-run history however short it is, so small inputs get few, long chunks rather
-    // than one sliver per CU (a 1 500-row contig: 3 chunks and 4 passes instead of 24 chunks and 15 passes)
-    if (lc <= 0) lc = (int)std::max<long long>(512, (rows + slots - 1) / slots);
-    chunks.clear();
-    max_chunks_per_contig = 1;
-    for (int c = 0; c < n_contigs; ++c) {
-        const int L = Ls[c];
-        const int nc = std::max(1, ceil_div(L, lc));
-        max_chunks_per_contig = std::max(max_chunks_per_contig, nc);
-        for (int j = 0; j < nc; ++j) {
-            Chunk ch;
-            ch.base = contig_base[c];
-            ch.r0 = (int)((long long)L * j / nc);
-            ch.r1 = (int)((long long)L * (j + 1) / nc);
-            ch.contig = c;
-            ch.first = (j == 0);
-            ch.last = (j == nc - 1);
-            ch.pad = 0;
-            ch.h0 = ch.h1 = ch.r0;               // (forward list; the backward copy below is given r1: no halo on this path)
-            chunks.push_back(ch);
+    std::vector<long long> cum;
+    auto cut = [&](const std::vector<int> &ncs, std::vector<Chunk> &out, bool bwd, long long halo_l, long long halo_d) {
+        out.clear();
+        for (int c = 0; c < n_contigs; ++c) {
+            const int L = Ls[c];
+            cum.assign((size_t)L + 1, 0);
+            for (int i = 1; i <= L; ++i) {
+                const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
+                cum[i] = cum[i - 1] + (ri.gid < 0 ? 1 : ss_row_cost(p, groups[ri.gid].span));
+            }
+            const int nc = ncs[c];
+            int prev = 0;
+            for (int j = 0; j < nc; ++j) {
+                int r1;
+                if (j == nc - 1) r1 = L;
+                else {
+                    const long long target = cum[L] * (j + 1) / nc;
+                    r1 = (int)(std::lower_bound(cum.begin(), cum.end(), target) - cum.begin());
+                    r1 = std::max(prev + 1, std::min(r1, L - (nc - 1 - j)));
+                }
+                Chunk ch;
+                ch.base = contig_base[c];
+                ch.r0 = prev; ch.r1 = r1; ch.contig = c;
+                ch.first = (j == 0); ch.last = (j == nc - 1); ch.pad = 0;
+                // halo rows (positions counted on this contig's cumulative costs): forward chunks look back, backward ones ahead
+                if (bwd) {
+                    const long long e1 = cum[r1] + halo_d, e0 = e1 + halo_l;
+                    ch.h1 = (int)std::min<long long>(L, std::lower_bound(cum.begin(), cum.end(), e1) - cum.begin());
+                    ch.h0 = (int)std::min<long long>(L, std::lower_bound(cum.begin(), cum.end(), e0) - cum.begin());
+                    if (halo_l + halo_d == 0 || ch.last) ch.h0 = ch.h1 = r1;
+                } else {
+                    const long long e1 = cum[prev] - halo_d, e0 = e1 - halo_l;
+                    ch.h1 = e1 <= 0 ? 0 : (int)(std::upper_bound(cum.begin(), cum.end(), e1) - cum.begin()) - 1;
+                    ch.h0 = e0 <= 0 ? 0 : (int)(std::upper_bound(cum.begin(), cum.end(), e0) - cum.begin()) - 1;
+                    ch.h1 = std::min(ch.h1, prev); ch.h0 = std::min(ch.h0, ch.h1);
+                    if (halo_l + halo_d == 0 || ch.first) ch.h0 = ch.h1 = prev;
+                }
+                out.push_back(ch);
+                prev = r1;
+            }
         }
-    }
-    max_pass = max_chunks_per_contig + 3;   // (+1: the full pass that follows an eigen-free pre-pass)
-    if (ss_static) max_pass += 4 + 2;       // light passes of the scan chains; a warm start numbers its passes from 1 or 2
-    chunks_b = chunks;
-    for (Chunk &cb : chunks_b) cb.h0 = cb.h1 = cb.r1;
-    ss_halo = false;
+    };
+    cut(p.chunks_fwd, chunks, false, p.halo_lf, p.halo_df);
+    cut(p.chunks_bwd, chunks_b, true, p.halo_lb, p.halo_db);
 }
 
 void smcpp_im::upload_chunk_state() {
@@ -1000,9 +1098,9 @@ void smcpp_im::upload_chunk_state() {
         const size_t nf = chunks.size(), nb = chunks_b.size();
         ss_tasks.clear();
         size_t i = 0, j = 0;
-        if (ss_hybrid && ss_dirsplit) {
+        if (plan.dirsplit()) {
             // single-direction workgroups, the two kinds interleaved in proportion
-            const size_t W = (size_t)ss_wg_waves;
+            const size_t W = (size_t)plan.wg_waves;
             while (i < nf || j < nb) {
                 const bool take_f = j >= nb || (i < nf && (double)i * (double)nb <= (double)j * (double)nf);
                 for (size_t q = 0; q < W; ++q) {
@@ -1017,12 +1115,12 @@ void smcpp_im::upload_chunk_state() {
             if (take_f) ss_tasks.push_back((int)i++);
             else ss_tasks.push_back((1 << 30) | (int)j++);
         }
-        while (ss_tasks.size() % ss_wg_waves) ss_tasks.push_back(-1);
+        while (ss_tasks.size() % plan.wg_waves) ss_tasks.push_back(-1);
         d_tasks.upload(ss_tasks, stream);
     }
     d_ends_f.alloc(2 * nch * Mp); d_used_f.alloc(nch * Mp);
     d_ends_b.alloc(2 * nch * Mp); d_used_b.alloc(nch * Mp);
-    d_changed_f.alloc(max_pass + 1); d_changed_b.alloc(max_pass + 1);
+    d_changed_f.alloc(plan.max_pass + 1); d_changed_b.alloc(plan.max_pass + 1);
     HIPCHK(hipStreamSynchronize(stream));
 }
 
@@ -1190,35 +1288,20 @@ void smcpp_im::make_slabs() {
     ek_slab_off[(size_t)n_contigs * Ke] = (int)slabs_ek.size();
 }
 
+// the operand buffers of the eigen-free pre-pass, where the plan takes it (ChainPlan::power_ok)
 void smcpp_im::setup_power() {
-    int mx = 0;
-    for (int g = 0; g < G; ++g) mx = std::max(mx, groups[g].span);
-    int longest = 0;
-    for (const Chunk &ch : chunks) longest = std::max(longest, ch.r1 - ch.r0);
-    const char *pe = opt().has(smcpp_opt::O_POWER_PREPASS) ? opt().str(smcpp_opt::O_POWER_PREPASS).c_str() : nullptr;
-    // spans below 32 (binned data: four squarings give every power); chunks short enough that pass 1 re-runs them whole
-    // anyway (the rows of the pre-pass are all overwritten: it runs in float and its normalisers carry no eigenvalue scale)
-    const bool coop_pre = chain_mode == 2 && Mp <= 64;
-    const bool big_pre = chain_mode == 3 && Mp > 64 && Mp <= 256;
-    // spans up to twelve bits (4095 positions); the cooperative chains read the powers beyond A^16 from L2 on the few rows
-    // that need them, the streamed-operand ones stream every power anyway
-    power_ok = (coop_pre || big_pre) && mx <= 4095 && Ke >= 1 && G >= 1 && longest <= 2000 && !(pe && atoi(pe) == 0) && !ss_static;
-    max_span_pw = mx;
-    pw_nbits = 5;
-    while ((1 << pw_nbits) <= mx) ++pw_nbits;
-    pw_npow = pw_nbits - 1;
-    if (!power_ok) return;
-    if (big_pre) {
+    if (!plan.power_ok) return;
+    if (plan.dense == ChainPlan::STREAMED_OPERANDS) {
         const size_t MM = (size_t)Mp * Mp;
-        d_W.alloc((size_t)Ke * pw_nbits * MM);
-        d_qBf.alloc((size_t)Ke * pw_nbits * MM);
-        d_qBb.alloc((size_t)Ke * pw_nbits * MM);
+        d_W.alloc((size_t)Ke * plan.pw_nbits * MM);
+        d_qBf.alloc((size_t)Ke * plan.pw_nbits * MM);
+        d_qBb.alloc((size_t)Ke * plan.pw_nbits * MM);
         d_pre_qTf.alloc(MM);
         d_pre_qTdT.alloc(MM);
         return;
     }
-    d_Bf.alloc((size_t)Ke * pw_npow * Mp * Mp);
-    d_Bb.alloc((size_t)Ke * pw_npow * Mp * Mp);
+    d_Bf.alloc((size_t)Ke * plan.pw_npow * Mp * Mp);
+    d_Bb.alloc((size_t)Ke * plan.pw_npow * Mp * Mp);
 }
 
 void smcpp_im::alloc_device() {
@@ -1245,29 +1328,10 @@ void smcpp_im::alloc_device() {
         HIPCHK(hipStreamSynchronize(s));
     }
     {
-        // scan chains: descriptors {key slot, span}; slot = frequency rank of the key (the emission vectors of the first
-        // ss_nlds slots live in LDS); same padding as above with span-1 rows of slot 0 (the scan chains request one descriptor per
-        // row, two rows ahead: they read two rows past either end of a contig and consume none of them)
-        std::vector<long long> kc(K, 0);
-        for (int c = 0; c < n_contigs; ++c)
-            for (int i = 1; i <= Ls[c]; ++i) kc[rowinfo[(size_t)contig_base[c] + i].kid]++;
-        std::vector<int> order(K);
-        for (int k = 0; k < K; ++k) order[k] = k;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return kc[x] > kc[y]; });
-        ss_slot_of_key.assign(K, 0);
-        for (int r = 0; r < K; ++r) ss_slot_of_key[order[r]] = r;
-        const int MS = 64 * NPL;
-        ss_nlds = (int)std::min<long long>(K, ((150 / std::max(1, ss_wpc)) * 1024) / ((long long)MS * 8));   // ss_wpc workgroups share a CU's 160 KB
-        // (until round 5 the table was capped at 64 KB: the 192 six-int keys of config C4 - 96 KB at M = 48 - left 64 slots to the L2 path
-        // and with them the kernel to its instantiation with vector-memory waits on every row: chains 0.86 -> see DESIGN.md section 6)
-        if (ss_hybrid) ss_nlds = (int)std::max<long long>(1, std::min<long long>(K, (long long)((ss_dirsplit ? 158 : 150) * 1024 - ss_tab_bytes()) / ((long long)MS * 8)));   // one workgroup per CU
-        ss_positions = 0;
-        for (int c = 0; c < n_contigs; ++c)
-            for (int i = 1; i <= Ls[c]; ++i) {
-                const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
-                ss_positions += ri.gid < 0 ? 1 : ss_row_cost(groups[ri.gid].span);
-            }
-        if (ss_static) {
+        // scan chains: descriptors {key slot, span} (slot: ss_slot_of_key, build_layout); same padding as above with span-1 rows of slot 0
+        // (the scan chains request one descriptor per row, two rows ahead: they read two rows past either end of a contig and
+        // consume none of them)
+        if (plan.scan) {
             std::vector<int2> rd((size_t)total_rows + 2 * ROWDESC_PAD, make_int2(0, 1));
             for (size_t r = 0; r < (size_t)total_rows; ++r) {
                 const RowInfo &ri = rowinfo[r];
@@ -1281,10 +1345,10 @@ void smcpp_im::alloc_device() {
                     for (int ell = 2; ell <= Ls[c]; ++ell)
                         if (piece_row[c][ell] == piece_row[c][ell - 1]) rd[ROWDESC_PAD + (size_t)contig_base[c] + ell].x |= SS_ROW_CONT;
             // rows of the jump key with room for a jump behind their first position (SS_ROW_JUMP: one scalar bit test per row in the kernel)
-            if (ss_jump_P)
+            if (plan.jump_P)
                 for (size_t r = 0; r < (size_t)total_rows; ++r) {
                     const RowInfo &ri = rowinfo[r];
-                    if (ri.gid >= 0 && groups[ri.gid].kid == ss_jump_kid && groups[ri.gid].span - 1 >= ss_jump_P) rd[ROWDESC_PAD + r].x |= SS_ROW_JUMP;
+                    if (ri.gid >= 0 && groups[ri.gid].kid == plan.jump_kid && groups[ri.gid].span - 1 >= plan.jump_P) rd[ROWDESC_PAD + r].x |= SS_ROW_JUMP;
                 }
             d_rowdesc_ss.upload(rd, s);
             HIPCHK(hipStreamSynchronize(s));

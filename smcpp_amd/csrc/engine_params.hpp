@@ -153,14 +153,14 @@ void smcpp_im::dev_prepare() {
         // chains expand position by position (ss_extract_generators' underflow bound, checked by the kernel)
         std::vector<int> ms_local(K, 1), local(Kp_, -1), slot(Kp_, -1), maxspan(Kp_, 1);
         for (const Group &gr : groups)
-            if (!(ss_hybrid && gr.span > ss_hyb_th)) ms_local[gr.kid] = std::max(ms_local[gr.kid], gr.span);
+            if (!(plan.hybrid && gr.span > plan.hyb_th)) ms_local[gr.kid] = std::max(ms_local[gr.kid], gr.span);
         for (int k = 0; k < K; ++k) {
             const int kg = have_global ? local_to_global[k] : k;
             local[kg] = k;
-            slot[kg] = (ss_static && (int)ss_slot_of_key.size() == K) ? ss_slot_of_key[k] : k;
+            slot[kg] = (plan.scan && (int)ss_slot_of_key.size() == K) ? ss_slot_of_key[k] : k;
             maxspan[kg] = ms_local[k];
         }
-        dprep->set_keys(*prep1, pk, Kp_, local, slot, maxspan, K, M, Mp, ss_static ? 64 * NPL : 0);
+        dprep->set_keys(*prep1, pk, Kp_, local, slot, maxspan, K, M, Mp, plan.scan ? 64 * NPL : 0);
     }
     T_lazy = T_from_gen = false;
     if (nder > 0) {
@@ -436,7 +436,7 @@ void smcpp_im::host_prep_and_upload() {
             gsc[g] = s_.scale;
             // (the eigenvalue powers (d_r / scale)^span of the group: k_group_dpow, on the device)
             // the scan steps apply the operator itself: their normalisers carry no eigenvalue scale (hybrid rows do: d / scale)
-            gls[g] = (ss_active && !(ss_hybrid && sp > ss_hyb_th)) ? 0.0 : sp * ls;
+            gls[g] = (ss_active && !(plan.hybrid && sp > plan.hyb_th)) ? 0.0 : sp * ls;
         }
     };
     // M >= 128: a team of threads per eigen key (nonsym_eig_team.hpp: bit-identical to the serial routine); the size follows
@@ -518,7 +518,7 @@ void smcpp_im::host_prep_and_upload() {
     auto tp1 = std::chrono::steady_clock::now();
     std::vector<float> qTf;
     std::vector<double> qTdT, qPinvT, qPT, qPrm, qPinvrm;
-    if (Mp > 64 && chain_mode == 3 && !ss_active) {          // (the scan chains stream no operand)
+    if (Mp > 64 && plan.dense == ChainPlan::STREAMED_OPERANDS && !ss_active) {          // (the scan chains stream no operand)
         // quarter-interleaved streaming layouts  Q[t][i][kq] = Mt[(kq*KQ + t)*Mp + i]  (k_fwd_big / k_bwd_big)
         const int KQ = Mp / 4;
         qTf.assign(MM, 0.f); qTdT.assign(MM, 0.0);

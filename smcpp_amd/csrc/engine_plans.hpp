@@ -109,7 +109,7 @@ static void launch_s1(int npl, const S1Args &a, hipStream_t s) {
     }
 }
 
-ChainArgs smcpp_im::chain_args() {
+ChainArgs smcpp_im::chain_args(const ChainPass &cp) {
     ChainArgs a;
     a.M = M; a.Mp = Mp; a.nchunks = (int)chunks.size(); a.pass = 0;
     a.hot = hot_eig; a.hot2 = hot_eig2; a.variant = 0;
@@ -121,20 +121,19 @@ ChainArgs smcpp_im::chain_args() {
     a.eps_f = eps_f; a.eps_b = eps_b;
     a.dbg = nullptr;
     a.warm_f = nullptr; a.warm_b = nullptr;
-    a.Bf = d_Bf.p; a.Bb = d_Bb.p; a.g_span = d_g_span.p; a.nbits = pw_nbits; a.npow = pw_npow;
-    a.prio = std::max(0, std::min(3, opt().i(smcpp_opt::O_BWD_PRIO, 1)));
+    a.Bf = d_Bf.p; a.Bb = d_Bb.p; a.g_span = d_g_span.p; a.nbits = plan.pw_nbits; a.npow = plan.pw_npow;
+    a.prio = cp.prio;
     a.changed = nullptr;
     return a;
 }
 
 // LDS budget of the cooperative kernels: exchange buffers + descriptors (+ the emission / eigenvalue-power tables when
 // they fit: TAB)
-static void coop_lds(int Mp, int K, int G, int &tab_c, size_t &shm_c) {
+static void coop_lds(int Mp, int K, int G, bool tab_allowed, int &tab_c, size_t &shm_c) {
     const int KQ = Mp / 4, UP = KQ + 2;
     const size_t base_c = (size_t)(4 * UP + 8 * UP) * 8 + 2 * Mp * 4 + 1024 + 64;
     const size_t tabs = ((size_t)K * 4 * UP + (size_t)G * Mp) * 8;      // backward layout of generation 1 is the larger one
-    tab_c = (base_c + tabs <= 64 * 1024) ? 1 : 0;
-    if (opt().has(smcpp_opt::O_COOP_TAB)) tab_c = tab_c && opt().i(smcpp_opt::O_COOP_TAB, 1) != 0;    // test hook: force the global-table path
+    tab_c = (base_c + tabs <= 64 * 1024 && tab_allowed) ? 1 : 0;        // (ChainPass::coop_tab = false: the global-table path forced)
     shm_c = base_c + (tab_c ? tabs : 0);
 }
 
@@ -144,7 +143,8 @@ void smcpp_im::stage_static_and_prepass() {
     ensure_T();
     prepass_launched = false;
     static_packed = false;
-    if (!power_ok || (warm_start && warm_valid)) return;
+    if (!plan.power_ok || (warm_start && warm_valid)) return;
+    const ChainPass cp = resolve_chain_pass();
     hipStream_t s = stream, sb = dual_stream ? stream2 : stream;
     const size_t MM = (size_t)Mp * Mp;
     auto ensure = [](auto &v, size_t n, auto init) { if (v.size() != n) v.assign(n, init); };
@@ -178,8 +178,8 @@ void smcpp_im::stage_static_and_prepass() {
         off += bytes;
         return dp;
     };
-    ChainArgs a = chain_args();
-    if (chain_mode == 3) {
+    ChainArgs a = chain_args(cp);
+    if (plan.dense == ChainPlan::STREAMED_OPERANDS) {
         // streamed-operand chains: pi, T (row-major) and the emission table go up, everything else is built on the device
         a.pi_f = reinterpret_cast<const float *>(put(hs_pi_f.data(), hs_pi_f.size() * 4));
         const double *pre_Td = reinterpret_cast<const double *>(put(hs_Td.data(), hs_Td.size() * 8));
@@ -189,14 +189,14 @@ void smcpp_im::stage_static_and_prepass() {
         d_changed_b.zero(s);
         const int nb = ceil_div((long long)MM, 256);
         hipLaunchKernelGGL(k_big_tq, dim3(nb), dim3(256), 0, s, Mp, pre_Td, d_pre_qTf.p, d_pre_qTdT.p);
-        hipLaunchKernelGGL(k_pow_init, dim3(nb, Ke), dim3(256), 0, s, M, Mp, pw_nbits, (const int *)d_e_kid.p, a.E, pre_Td, d_W.p);
-        for (int b = 0; b + 1 < pw_nbits; ++b) {
+        hipLaunchKernelGGL(k_pow_init, dim3(nb, Ke), dim3(256), 0, s, M, Mp, plan.pw_nbits, (const int *)d_e_kid.p, a.E, pre_Td, d_W.p);
+        for (int b = 0; b + 1 < plan.pw_nbits; ++b) {
             hipLaunchKernelGGL(k_sq_f64, dim3(Mp / 16, Mp / 16, Ke), dim3(64), 0, s, Mp, (const double *)(d_W.p + (size_t)b * MM),
-                               d_W.p + (size_t)(b + 1) * MM, (size_t)pw_nbits * MM);
+                               d_W.p + (size_t)(b + 1) * MM, (size_t)plan.pw_nbits * MM);
             if (b + 1 >= 5)
-                hipLaunchKernelGGL(k_pow_rescale, dim3(Ke), dim3(256), 0, s, Mp, d_W.p + (size_t)(b + 1) * MM, (size_t)pw_nbits * MM);
+                hipLaunchKernelGGL(k_pow_rescale, dim3(Ke), dim3(256), 0, s, Mp, d_W.p + (size_t)(b + 1) * MM, (size_t)plan.pw_nbits * MM);
         }
-        hipLaunchKernelGGL(k_pow_layout, dim3(nb, Ke * pw_nbits), dim3(256), 0, s, Mp, (const double *)d_W.p, d_qBf.p, d_qBb.p);
+        hipLaunchKernelGGL(k_pow_layout, dim3(nb, Ke * plan.pw_nbits), dim3(256), 0, s, Mp, (const double *)d_W.p, d_qBf.p, d_qBb.p);
         pre_bargs = BigArgs();
         pre_bargs.qTf = d_pre_qTf.p; pre_bargs.qTdT = d_pre_qTdT.p;
         pre_bargs.qPinvT = pre_bargs.qPT = pre_bargs.qPrm = pre_bargs.qPinvrm = nullptr;
@@ -230,7 +230,7 @@ void smcpp_im::stage_static_and_prepass() {
         const size_t shm = (size_t)(2 * Mp * (Mp + 1) + 8) * sizeof(double);
         switch (Mp) {
 #define P_(x) case x: { static bool once = false; if (!once) { HIPCHK(hipFuncSetAttribute((const void *)k_binary_powers<x>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); once = true; } \
-                    hipLaunchKernelGGL(k_binary_powers<x>, dim3(Ke), dim3(256), shm, s, M, pw_npow, (const int *)d_e_kid.p, a.E, pre_Td, d_Bf.p, d_Bb.p); } break;
+                    hipLaunchKernelGGL(k_binary_powers<x>, dim3(Ke), dim3(256), shm, s, M, plan.pw_npow, (const int *)d_e_kid.p, a.E, pre_Td, d_Bf.p, d_Bb.p); } break;
             P_(16) P_(32) P_(48) P_(64)
 #undef P_
             default: throw std::runtime_error("internal: power pre-pass with an unsupported state count");
@@ -239,13 +239,13 @@ void smcpp_im::stage_static_and_prepass() {
     const int dbg_level = opt().i(smcpp_opt::O_POWER_DEBUG, 0);
     if (dbg_level == 1) { HIPCHK(hipStreamSynchronize(s)); fprintf(stderr, "[power] powers ok\n"); static_packed = false; return; }
     int tab_c; size_t shm_c;
-    coop_lds(Mp, K, G, tab_c, shm_c);
+    coop_lds(Mp, K, G, cp.coop_tab, tab_c, shm_c);
     CoopArgs cargs;
     cargs.K = K; cargs.G = G;
     cargs.power_off = (int)shm_c;          // two scratch vectors behind the regular carve-up
     shm_c += 2048;
     a.variant = 1; a.pass = 0;
-    if (!(opt().i(smcpp_opt::O_BWD_PRIO_MASK, 7) & 1)) a.prio = 0;
+    if (!(cp.prio_mask & 1)) a.prio = 0;
     if (sb != s) {
         HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], s));
         HIPCHK(hipStreamWaitEvent(sb, ev[EV_CHAIN_SYNC], 0));
@@ -265,7 +265,14 @@ void smcpp_im::stage_static_and_prepass() {
 
 void smcpp_im::run_chains() {
     hipStream_t s = stream;
-    ChainArgs a = chain_args();
+    // what this E-step decides on top of the plan: the passes launched up front, the second stream, the backward chain's issue
+    // priority, the warm start (where the buffers of the previous E-step fit this chunk list)
+    const ChainPass cp = resolve_chain_pass();
+    int want_f = cp.want_f, want_b = cp.want_b;
+    const int prio_mask = cp.prio_mask;
+    const bool dual = cp.dual;
+    const bool warm = cp.warm && d_warm_f.n == chunks.size() * (size_t)Mp && d_warm_b.n == chunks.size() * (size_t)Mp;
+    ChainArgs a = chain_args(cp);
     CoopArgs cargs;
     cargs.K = K; cargs.G = G; cargs.power_off = 0;
     BigArgs bargs;
@@ -273,9 +280,7 @@ void smcpp_im::run_chains() {
     bargs.qPrm = d_qPrm.p; bargs.qPinvrm = d_qPinvrm.p; bargs.qBf = nullptr; bargs.qBb = nullptr;
     size_t shm_c = 0;
     int tab_c = 0;
-    coop_lds(Mp, K, G, tab_c, shm_c);
-    const bool warm = warm_start && warm_valid && chain_mode == 2 && Mp <= 64 &&
-                      d_warm_f.n == chunks.size() * (size_t)Mp && d_warm_b.n == chunks.size() * (size_t)Mp;
+    coop_lds(Mp, K, G, cp.coop_tab, tab_c, shm_c);
     a.warm_f = warm ? d_warm_f.p : nullptr;
     a.warm_b = warm ? d_warm_b.p : nullptr;
     if (opt().has(smcpp_opt::O_DEBUG_CYCLES)) { d_dbg.alloc(16); d_dbg.zero(s); a.dbg = d_dbg.p; }
@@ -284,37 +289,39 @@ void smcpp_im::run_chains() {
         d_changed_f.zero(s);
         d_changed_b.zero(s);
     }
-    if (h_flags_cap < 2 * (max_pass + 1)) {
+    if (h_flags_cap < 2 * (plan.max_pass + 1)) {
         if (h_flags) (void)hipHostFree(h_flags);
-        h_flags_cap = 2 * (max_pass + 1);
+        h_flags_cap = 2 * (plan.max_pass + 1);
         HIPCHK(hipHostMalloc((void **)&h_flags, sizeof(int) * h_flags_cap, hipHostMallocCoherent | hipHostMallocMapped));
         d_flags_view = nullptr;
     }
-    int *chf = h_flags, *chb = h_flags + (max_pass + 1);
+    int *chf = h_flags, *chb = h_flags + (plan.max_pass + 1);
     auto first_quiet = [](const int *ch, int upto) {
         for (int j = 0; j < upto; ++j)
             if (ch[j] == 0) return j;
         return -1;
     };
     int launched_f = pre ? 1 : 0, launched_b = pre ? 1 : 0;
-    int want_f = std::min(max_pass, last_fwd_passes > 0 ? last_fwd_passes + 1 : std::min(max_pass, 8));
-    int want_b = std::min(max_pass, last_bwd_passes > 0 ? last_bwd_passes + 1 : std::min(max_pass, 8));
-    const size_t nel_ends = chunks.size() * (size_t)Mp;
     // after a pre-pass, pass 1 is a FULL pass from the pre-pass's end vectors (no skip test, no merge exit): every stored
     // row then comes from the exact kernels
     // issue priority of the backward wavefronts per pass (SMCPP_BWD_PRIO_MASK: bit 0 pre-pass, bit 1 the full pass after
     // it, bit 2 every other pass)
-    const int prio_mask = opt().i(smcpp_opt::O_BWD_PRIO_MASK, 7);
     const int prio0 = a.prio;
     auto set_variant = [&](int pass) {
         a.pass = pass;
-        if (pre && pass == 1) { a.variant = 2; a.warm_f = d_ends_f.p; a.warm_b = d_ends_b.p; (void)nel_ends; a.prio = (prio_mask & 2) ? prio0 : 0; }
+        if (pre && pass == 1) { a.variant = 2; a.warm_f = d_ends_f.p; a.warm_b = d_ends_b.p; a.prio = (prio_mask & 2) ? prio0 : 0; }
         else { a.variant = 0; a.warm_f = warm ? d_warm_f.p : nullptr; a.warm_b = warm ? d_warm_b.p : nullptr; a.prio = (prio_mask & 4) ? prio0 : 0; }
     };
     // The two chains are independent (beta does not depend on alpha).  The cooperative kernels leave most of a CU's
     // LDS and issue slots idle, so the backward passes run on a second stream and share the CUs with the forward ones.
-    const bool dual = dual_stream && ((chain_mode == 2 && Mp <= 64) || chain_mode == 4 || Mp > 64);
     hipStream_t sb = dual ? stream2 : s;
+    // one pass of one chain on the family's kernels
+    auto launch_pass = [&](bool fwd, hipStream_t st) {
+        if (!(plan.dense == ChainPlan::LOCK_STEP && launch_chain_lock(fwd, Mp, a, st)) &&
+            !(plan.dense == ChainPlan::STREAMED_OPERANDS && launch_chain_big(fwd, Mp, a, bargs, st)) &&
+            !(plan.dense == ChainPlan::COOPERATIVE && launch_chain_coop(fwd, Mp, a, cargs, tab_c, shm_c, st)))
+            throw std::runtime_error("internal: no dense chain kernel for this number of hidden states");
+    };
     if (dual) {
         HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], s));              // parameters / zeroed flags are ready on the main stream
         HIPCHK(hipStreamWaitEvent(sb, ev[EV_CHAIN_SYNC], 0));
@@ -328,10 +335,7 @@ void smcpp_im::run_chains() {
             a.changed = d_changed_f.p;
             for (; launched_f < want_f; ++launched_f) {
                 set_variant(launched_f);
-                if (!(chain_mode == 4 && launch_chain_lock(true, Mp, a, s)) &&
-                    !(chain_mode == 3 && launch_chain_big(true, Mp, a, bargs, s)) &&
-                    !(chain_mode == 2 && launch_chain_coop(true, Mp, a, cargs, tab_c, shm_c, s)))
-                    throw std::runtime_error("internal: no dense chain kernel for this number of hidden states");
+                launch_pass(true, s);
             }
         }
         if (first_round) HIPCHK(hipEventRecord(ev[EV_BWD_START], dual ? sb : s));
@@ -339,16 +343,13 @@ void smcpp_im::run_chains() {
             a.changed = d_changed_b.p;
             for (; launched_b < want_b; ++launched_b) {
                 set_variant(launched_b);
-                if (!(chain_mode == 4 && launch_chain_lock(false, Mp, a, sb)) &&
-                    !(chain_mode == 3 && launch_chain_big(false, Mp, a, bargs, sb)) &&
-                    !(chain_mode == 2 && launch_chain_coop(false, Mp, a, cargs, tab_c, shm_c, sb)))
-                    throw std::runtime_error("internal: no dense chain kernel for this number of hidden states");
+                launch_pass(false, sb);
             }
         }
         HIPCHK(hipGetLastError());
         if (first_round && dual) HIPCHK(hipEventRecord(ev[EV_FWD_END], s));      // end of the first batch of forward passes
-        HIPCHK(hipMemcpyAsync(chf, d_changed_f.p, sizeof(int) * (max_pass + 1), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(chb, d_changed_b.p, sizeof(int) * (max_pass + 1), hipMemcpyDeviceToHost, sb));
+        HIPCHK(hipMemcpyAsync(chf, d_changed_f.p, sizeof(int) * (plan.max_pass + 1), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(chb, d_changed_b.p, sizeof(int) * (plan.max_pass + 1), hipMemcpyDeviceToHost, sb));
         if (dual) {
             HIPCHK(hipEventRecord(ev[EV_CHAIN_SYNC], sb));
             HIPCHK(hipStreamWaitEvent(s, ev[EV_CHAIN_SYNC], 0));   // the statistics (main stream) need both chains
@@ -364,12 +365,12 @@ void smcpp_im::run_chains() {
         first_round = false;
         fq = first_quiet(chf, launched_f);
         bq = first_quiet(chb, launched_b);
-        fdone = fq >= 0 || launched_f >= max_pass;
-        bdone = bq >= 0 || launched_b >= max_pass;
+        fdone = fq >= 0 || launched_f >= plan.max_pass;
+        bdone = bq >= 0 || launched_b >= plan.max_pass;
         if (fdone && bdone) break;
         stats_enqueued = false;             // more passes follow: whatever was queued is stale
-        if (!fdone) want_f = std::min(max_pass, launched_f + 4);
-        if (!bdone) want_b = std::min(max_pass, launched_b + 4);
+        if (!fdone) want_f = std::min(plan.max_pass, launched_f + 4);
+        if (!bdone) want_b = std::min(plan.max_pass, launched_b + 4);
     }
     chains_dual = dual;
     if (a.dbg) {
@@ -381,7 +382,7 @@ void smcpp_im::run_chains() {
     if (fq < 0 || bq < 0) { stats_enqueued = false; throw std::runtime_error("chunk-boundary iteration did not converge"); }
     last_fwd_passes = fq;
     last_bwd_passes = bq;
-    if (warm_start && chain_mode == 2 && Mp <= 64) {
+    if (warm_start && plan.dense == ChainPlan::COOPERATIVE && Mp <= 64) {
         // every pass after the first quiet one only copies the boundary vectors forward: the buffer of the last
         // launched pass holds the converged ones
         const size_t nel = chunks.size() * (size_t)Mp;
@@ -503,7 +504,7 @@ bool smcpp_im::ss_extract_generators() {
     // a row of span s applies its operator s times without rescaling: keep clear of underflow
     // (a device-prepared table is checked by the kernel that forms it: DevPrep flag 2, looked at when the E-step has drained)
     if (!E_on_dev) for (const Group &gr : groups) {
-        if (ss_hybrid && gr.span > ss_hyb_th) continue;          // an eigen-power step, not `span` scan steps
+        if (plan.hybrid && gr.span > plan.hyb_th) continue;          // an eigen-power step, not `span` scan steps
         double mn = 1.0;
         for (int i = 0; i < M; ++i) mn = std::min(mn, E[(size_t)gr.kid * M + i]);
         if (!(mn > 0.0) || (double)gr.span * std::log(mn) < -450.0) return false;
@@ -516,52 +517,102 @@ static void launch_chain_ss_tt(const SsArgs &a, int ntasks, size_t shm, hipStrea
     lds_limit_once<k_chain_ss<NPL_, HYB_, ALL_, H32_>>();
     hipLaunchKernelGGL((k_chain_ss<NPL_, HYB_, ALL_, H32_>), dim3(ntasks / wgw), dim3(64 * wgw), shm, s, a);
 }
-// M <= 32 with one state per lane, no hybrid rows and every key slot in LDS: the instantiation whose scans skip the level that would only
-// move zeros (SMCPP_SS_H32=0: the full-width form there too).  describe() reports it as "two_row_scans".
-static bool ss_two_row_scans(int npl, bool hyb, int K, int nlds, int Mp) {
-    return npl == 1 && !hyb && K <= nlds && Mp <= 32 && !opt().off(smcpp_opt::O_SS_H32);
-}
+// The instantiation the plan names (ChainPlan::all_keys_in_lds, two_row_scans; describe() reports the latter)
 template <int NPL_, bool HYB_>
-static void launch_chain_ss_t(const SsArgs &a, int ntasks, size_t shm, hipStream_t s, int wgw) {
-    // every key slot in LDS (the usual case): the instantiation without the global path of the emission vectors
-    if (ss_two_row_scans(NPL_, HYB_, a.K, a.nlds, a.Mp)) launch_chain_ss_tt<NPL_, HYB_, true, NPL_ == 1 && !HYB_>(a, ntasks, shm, s, wgw);
-    else if (a.K <= a.nlds) launch_chain_ss_tt<NPL_, HYB_, true>(a, ntasks, shm, s, wgw);
-    else launch_chain_ss_tt<NPL_, HYB_, false>(a, ntasks, shm, s, wgw);
+static void launch_chain_ss_t(const ChainPlan &p, const SsArgs &a, int ntasks, size_t shm, hipStream_t s) {
+    if (p.two_row_scans) launch_chain_ss_tt<NPL_, HYB_, true, NPL_ == 1 && !HYB_>(a, ntasks, shm, s, p.wg_waves);
+    else if (p.all_keys_in_lds) launch_chain_ss_tt<NPL_, HYB_, true>(a, ntasks, shm, s, p.wg_waves);
+    else launch_chain_ss_tt<NPL_, HYB_, false>(a, ntasks, shm, s, p.wg_waves);
 }
-static void launch_chain_ss(int npl, const SsArgs &a, int ntasks, size_t shm, hipStream_t s, int wgw = 4) {
+static void launch_chain_ss(const ChainPlan &p, int npl, const SsArgs &a, int ntasks, size_t shm, hipStream_t s) {
     switch (npl) {
-        case 1: if (a.hyb_th != 0x7fffffff) launch_chain_ss_t<1, true>(a, ntasks, shm, s, wgw); else launch_chain_ss_t<1, false>(a, ntasks, shm, s, 4); break;
-        case 2: launch_chain_ss_t<2, false>(a, ntasks, shm, s, 4); break;
-        case 3: launch_chain_ss_t<3, false>(a, ntasks, shm, s, 4); break;
-        case 4: launch_chain_ss_t<4, false>(a, ntasks, shm, s, 4); break;
-        case 8: launch_chain_ss_t<8, false>(a, ntasks, shm, s, 4); break;
-        case 16: launch_chain_ss_t<16, false>(a, ntasks, shm, s, 4); break;
+        case 1: if (p.hybrid) launch_chain_ss_t<1, true>(p, a, ntasks, shm, s); else launch_chain_ss_t<1, false>(p, a, ntasks, shm, s); break;
+        case 2: launch_chain_ss_t<2, false>(p, a, ntasks, shm, s); break;
+        case 3: launch_chain_ss_t<3, false>(p, a, ntasks, shm, s); break;
+        case 4: launch_chain_ss_t<4, false>(p, a, ntasks, shm, s); break;
+        case 8: launch_chain_ss_t<8, false>(p, a, ntasks, shm, s); break;
+        case 16: launch_chain_ss_t<16, false>(p, a, ntasks, shm, s); break;
         default: throw std::runtime_error("unsupported number of hidden states");
     }
 }
 
 
 void smcpp_im::ss_launch_passes(int upto) {
-    const size_t shm = (size_t)ss_nlds * 64 * NPL * sizeof(double) + ss_tab_bytes();
+    const size_t shm = (size_t)plan.nlds * 64 * NPL * sizeof(double) + ss_tab_bytes(plan, Mp);
     for (; ss_launched < upto; ++ss_launched) {
         // per direction: `light` store-free float passes (history), then one full pass from their end vectors, then re-run
         // passes; without light passes the first pass is the full one (from pi / the uniform vector)
         const int p = ss_launched;
-        const bool lf = p < ss_light_f, lb = p < ss_light_b;
+        const bool lf = p < chain_pass.light_f, lb = p < chain_pass.light_b;
         ss_args.pass = p;
         ss_args.mode_f = lf ? 2 : p == 0 ? 0 : 1;
         ss_args.mode_b = lb ? 2 : p == 0 ? 0 : 1;
-        ss_args.full_f = (p > 0 && p == ss_light_f) ? 1 : 0;
-        ss_args.full_b = (p > 0 && p == ss_light_b) ? 1 : 0;
-        launch_chain_ss(NPL, ss_args, (int)ss_tasks.size(), shm, stream, ss_wg_waves);
+        ss_args.full_f = (p > 0 && p == chain_pass.light_f) ? 1 : 0;
+        ss_args.full_b = (p > 0 && p == chain_pass.light_b) ? 1 : 0;
+        launch_chain_ss(plan, NPL, ss_args, (int)ss_tasks.size(), shm, stream);
     }
     HIPCHK(hipGetLastError());
+}
+
+// What this E-step decides on top of the plan; with resolve_chain_plan the only reader of the chain phase's switches.
+ChainPass smcpp_im::resolve_chain_pass() const {
+    ChainPass cp;
+    const bool several = chunks.size() > (size_t)n_contigs && chunks_b.size() > (size_t)n_contigs;   // chunks per contig, both directions
+    const bool warm = warm_start && ss_warm_valid;
+    // All scans of the stored passes in float (chains_ss.hpp: ss_x_scan_fwd / ss_x_scan_bwd), the default since round 5 for one
+    // state per lane; SMCPP_SS_MIXED=0 keeps the fp64 scans (tests and bench.py's `value_ref_width` compare the two).
+    // Round 6: with save_gamma as well - the decoded index of EVERY column of the two full-size binned contigs (471 106 columns,
+    // goldens G19) equals the compiled reference's under the float scans (tests/test_gpu_argmax.py), so the path that is timed and
+    // the path whose indices are checked are the same arithmetic.
+    cp.mixed = !opt().off(smcpp_opt::O_SS_MIXED) && NPL == 1 && !plan.hybrid;
+    {
+        // light passes: enough of them that the full pass starts ~11 e-folds of history in (the chains forget with an e-fold of
+        // ~240 positions forward, ~340 backward on the benchmark model); none when the chunks are long against that
+        const int ef = opt().i(smcpp_opt::O_SS_LIGHT_F, -1), eb = opt().i(smcpp_opt::O_SS_LIGHT_B, -1);
+        const long long pos = plan.positions / std::max<size_t>(1, chunks.size());
+        const long long pos_b = plan.positions / std::max<size_t>(1, chunks_b.size());
+        auto pick = [&](double hist, long long p_) { return p_ <= 0 || (double)p_ > 1.5 * hist ? 0 : std::min(4, (int)std::ceil(hist / (double)p_)); };
+        cp.light_f = ef >= 0 ? ef : pick(2800.0, pos);
+        cp.light_b = eb >= 0 ? eb : pick(3900.0, pos_b);
+        if (chunks.size() <= (size_t)n_contigs) cp.light_f = 0;      // one chunk per contig: nothing to iterate
+        if (chunks_b.size() <= (size_t)n_contigs) cp.light_b = 0;
+    }
+    if (plan.hybrid) cp.light_f = cp.light_b = 0;      // (the light passes have no eigen-power step; un-binned inputs have long chunks)
+    // halo pass: the first pass enters every chunk through its halo and stores rows that are already exact; no light passes
+    cp.use_halo = plan.halo && !warm && several;
+    if (cp.use_halo) cp.light_f = cp.light_b = 0;
+    if (warm && several) {
+        // the boundary vectors of the previous E-step are exact for ITS parameters, i.e. off by the parameter step instead of by
+        // O(1): they replace one light pass; every stored row still comes from the full fp64 pass on the new parameters
+        cp.pass0 = ss_warm_parity == 0 ? 1 : 2;
+        cp.light_f = cp.pass0 + std::max(0, cp.light_f - 1);
+        cp.light_b = cp.pass0 + std::max(0, cp.light_b - 1);
+    }
+    cp.jump = ss_jump_on();
+    // (round 5) the passes launched up front end with the pass that is expected to rewrite no end vector - the all-skip pass behind
+    // it (0.01 ms of kernel + its place in the queue) is not launched: run_chains_ss certifies from the end-vector flags
+    cp.cert_up_front = opt().on(smcpp_opt::O_SS_CERT_PASS) || ss_need_cert_pass;
+    // (never fewer than one re-run pass behind the pass that stores everything - that one always rewrites its end vectors: with one
+    // chunk per contig, or boundaries that were already exact, the quiet pass IS that re-run pass)
+    cp.want = std::min(plan.max_pass, std::max(cp.pass0 + (last_ss_passes > 0 ? last_ss_passes + (cp.cert_up_front ? 1 : 0) : 6),
+                                               std::max(cp.light_f, cp.light_b) + 2));
+    // the dense families: passes launched up front (sized from the previous E-step), the backward chain on a second stream, its
+    // issue priority (SMCPP_BWD_PRIO: s_setprio 0..3) and the passes that raise it, the warm start, the LDS tables (test hook)
+    cp.want_f = std::min(plan.max_pass, last_fwd_passes > 0 ? last_fwd_passes + 1 : std::min(plan.max_pass, 8));
+    cp.want_b = std::min(plan.max_pass, last_bwd_passes > 0 ? last_bwd_passes + 1 : std::min(plan.max_pass, 8));
+    cp.dual = dual_stream && ((plan.dense == ChainPlan::COOPERATIVE && Mp <= 64) || plan.dense == ChainPlan::LOCK_STEP || Mp > 64);
+    cp.prio = std::max(0, std::min(3, opt().i(smcpp_opt::O_BWD_PRIO, 1)));
+    cp.prio_mask = opt().i(smcpp_opt::O_BWD_PRIO_MASK, 7);
+    cp.warm = warm_start && warm_valid && plan.dense == ChainPlan::COOPERATIVE && Mp <= 64;
+    cp.coop_tab = !opt().has(smcpp_opt::O_COOP_TAB) || opt().i(smcpp_opt::O_COOP_TAB, 1) != 0;
+    return cp;
 }
 
 // Upload pi, the generators and the emission vectors (by key slot) and start the passes: nothing here needs an eigensystem,
 // so the host solves the eigenproblems of the statistics while the chains run.
 void smcpp_im::ss_launch_initial() {
     hipStream_t s = stream;
+    const ChainPass &cp = chain_pass = resolve_chain_pass();
     const int MS = 64 * NPL;
     std::vector<float> &pi_f = hs_pi_f;
     if (pi_f.size() != (size_t)Mp) pi_f.assign(Mp, 0.f);
@@ -584,7 +635,7 @@ void smcpp_im::ss_launch_initial() {
     };
     SsArgs &a = ss_args;
     a = SsArgs();
-    a.M = M; a.Mp = Mp; a.nchunks = (int)chunks.size(); a.pass = 0; a.K = K; a.nlds = ss_nlds;
+    a.M = M; a.Mp = Mp; a.nchunks = (int)chunks.size(); a.pass = 0; a.K = K; a.nlds = plan.nlds;
     a.chunks = d_chunks.p; a.rowdesc = d_rowdesc_ss.p + ROWDESC_PAD;
     a.chunks_b = d_chunks_b.p; a.nchunks_b = (int)chunks_b.size(); a.tasks = d_tasks.p;
     a.pi_f = reinterpret_cast<const float *>(put(pi_f.data(), pi_f.size() * 4));
@@ -602,11 +653,11 @@ void smcpp_im::ss_launch_initial() {
     a.ends_f = d_ends_f.p; a.used_f = d_used_f.p; a.ends_b = d_ends_b.p; a.used_b = d_used_b.p;
     {
         // the per-pass flags live in pinned host memory: written by the kernels through its device view, cleared and read by the host
-        // ([0, max_pass]: "a chunk of the forward chain re-ran", then the same of the backward chain, then the two "an end vector
+        // ([0, plan.max_pass]: "a chunk of the forward chain re-ran", then the same of the backward chain, then the two "an end vector
         // was rewritten" arrays of the scan chains)
-        if (h_flags_cap < 4 * (max_pass + 1)) {
+        if (h_flags_cap < 4 * (plan.max_pass + 1)) {
             if (h_flags) (void)hipHostFree(h_flags);
-            h_flags_cap = 4 * (max_pass + 1);
+            h_flags_cap = 4 * (plan.max_pass + 1);
             HIPCHK(hipHostMalloc((void **)&h_flags, sizeof(int) * h_flags_cap, hipHostMallocCoherent | hipHostMallocMapped));
             d_flags_view = nullptr;
         }
@@ -618,50 +669,17 @@ void smcpp_im::ss_launch_initial() {
         }
         std::memset(h_flags, 0, sizeof(int) * h_flags_cap);
     }
-    a.changed_f = d_flags_view; a.changed_b = d_flags_view + (max_pass + 1);
-    a.endchg_f = d_flags_view + 2 * (max_pass + 1); a.endchg_b = d_flags_view + 3 * (max_pass + 1);
+    a.changed_f = d_flags_view; a.changed_b = d_flags_view + (plan.max_pass + 1);
+    a.endchg_f = d_flags_view + 2 * (plan.max_pass + 1); a.endchg_b = d_flags_view + 3 * (plan.max_pass + 1);
     a.eps_f = eps_f; a.eps_b = eps_b; a.full_f = a.full_b = 0;
-    {
-        // All scans of the stored passes in float (chains_ss.hpp: ss_x_scan_fwd / ss_x_scan_bwd), the default since round 5 for one
-        // state per lane; SMCPP_SS_MIXED=0 keeps the fp64 scans (tests and bench.py's `value_ref_width` compare the two).
-        // Round 6: with save_gamma as well - the decoded index of EVERY column of the two full-size binned contigs (471 106 columns,
-        // goldens G19) equals the compiled reference's under the float scans (tests/test_gpu_argmax.py), so the path that is timed and
-        // the path whose indices are checked are the same arithmetic.
-        const bool mixed_on = !opt().off(smcpp_opt::O_SS_MIXED);
-        a.mixed = (mixed_on && NPL == 1 && !ss_hybrid) ? 1 : 0;
-    }
-    if (ss_hybrid) {
-        a.hyb_th = ss_hyb_th; a.Ke = Ke; a.hot_ek = std::max(0, hot_eig); a.dirsplit = ss_dirsplit ? 1 : 0;
-        a.nk_lds = ss_nk_lds;
-        for (int e = 0; e < 4; ++e) { a.key_of_slot[e] = ss_ekey_of_slot[e]; a.slot_of_key[e] = ss_eslot_of_key[e]; }
+    a.mixed = cp.mixed ? 1 : 0;
+    if (plan.hybrid) {
+        a.hyb_th = plan.hyb_th; a.Ke = Ke; a.hot_ek = std::max(0, hot_eig); a.dirsplit = plan.dirsplit() ? 1 : 0;
+        a.nk_lds = plan.nk_lds;
+        for (int e = 0; e < 4; ++e) { a.key_of_slot[e] = plan.ekey_of_slot[e]; a.slot_of_key[e] = plan.eslot_of_key[e]; }
         a.Pinvrm = d_Pinvrm.p; a.Prm = d_Prm.p; a.PinvT = d_PinvT.p; a.PT = d_PT.p; a.dsc = d_dsc.p;
     }
-    {
-        // light passes: enough of them that the full pass starts ~11 e-folds of history in (the chains forget with an e-fold of
-        // ~240 positions forward, ~340 backward on the benchmark model); none when the chunks are long against that
-        long long pos = 0;
-        const int ef = opt().i(smcpp_opt::O_SS_LIGHT_F, -1), eb = opt().i(smcpp_opt::O_SS_LIGHT_B, -1);
-        pos = ss_positions / std::max<size_t>(1, chunks.size());
-        const long long pos_b = ss_positions / std::max<size_t>(1, chunks_b.size());
-        auto pick = [&](double hist, long long p_) { return p_ <= 0 || (double)p_ > 1.5 * hist ? 0 : std::min(4, (int)std::ceil(hist / (double)p_)); };
-        ss_light_f = ef >= 0 ? ef : pick(2800.0, pos);
-        ss_light_b = eb >= 0 ? eb : pick(3900.0, pos_b);
-        if (chunks.size() <= (size_t)n_contigs) ss_light_f = 0;      // one chunk per contig: nothing to iterate
-        if (chunks_b.size() <= (size_t)n_contigs) ss_light_b = 0;
-    }
-    if (ss_hybrid) ss_light_f = ss_light_b = 0;      // (the light passes have no eigen-power step; un-binned inputs have long chunks)
-    // halo pass: the first pass enters every chunk through its halo and stores rows that are already exact; no light passes
-    const bool use_halo = ss_halo && !(warm_start && ss_warm_valid) && chunks.size() > (size_t)n_contigs && chunks_b.size() > (size_t)n_contigs;
-    if (use_halo) ss_light_f = ss_light_b = 0;
-    a.halo = use_halo ? 1 : 0;
-    ss_pass0 = 0;
-    if (warm_start && ss_warm_valid && chunks.size() > (size_t)n_contigs && chunks_b.size() > (size_t)n_contigs) {
-        // the boundary vectors of the previous E-step are exact for ITS parameters, i.e. off by the parameter step instead of by
-        // O(1): they replace one light pass; every stored row still comes from the full fp64 pass on the new parameters
-        ss_pass0 = ss_warm_parity == 0 ? 1 : 2;
-        ss_light_f = ss_pass0 + std::max(0, ss_light_f - 1);
-        ss_light_b = ss_pass0 + std::max(0, ss_light_b - 1);
-    }
+    a.halo = cp.use_halo ? 1 : 0;
     ss_warm_valid = false;                     // (set again when this E-step's chains have converged)
     a.dbg = nullptr;
     if (opt().has(smcpp_opt::O_DEBUG_CYCLES)) { d_dbg.alloc(16); d_dbg.zero(s); a.dbg = d_dbg.p; }
@@ -670,25 +688,16 @@ void smcpp_im::ss_launch_initial() {
     {
         // Power jumps: the table of this E-step's operator power is built here, behind the upload above and the device-prepared
         // emission table, in front of the first pass - 64 wavefronts x P dependent scan steps (k_ss_jump_tables)
-        ss_jump_launch = false;
         a.jump = 0;
-        if (ss_jump_on()) {
-            ss_jump_launch = true;
+        if (cp.jump) {
             d_jtab_f.alloc(2 * 64 * 64);
             d_jdiag.alloc(64);
-            a.jump = ss_jump_P; a.jtab_f = d_jtab_f.p; a.jtab_t = d_jtab_f.p + 64 * 64; a.jdiag = d_jdiag.p;
-            hipLaunchKernelGGL(k_ss_jump_tables, dim3(16), dim3(256), 0, s, a, ss_slot_of_key[ss_jump_kid], d_jtab_f.p, d_jtab_f.p + 64 * 64, d_jdiag.p);
+            a.jump = plan.jump_P; a.jtab_f = d_jtab_f.p; a.jtab_t = d_jtab_f.p + 64 * 64; a.jdiag = d_jdiag.p;
+            hipLaunchKernelGGL(k_ss_jump_tables, dim3(16), dim3(256), 0, s, a, ss_slot_of_key[plan.jump_kid], d_jtab_f.p, d_jtab_f.p + 64 * 64, d_jdiag.p);
         }
     }
-    ss_launched = ss_pass0;
-    // (round 5) the passes launched up front end with the pass that is expected to rewrite no end vector - the all-skip pass behind
-    // it (0.01 ms of kernel + its place in the queue) is not launched: run_chains_ss certifies from the end-vector flags
-    const bool cert_launch = opt().on(smcpp_opt::O_SS_CERT_PASS);
-    // (never fewer than one re-run pass behind the pass that stores everything - that one always rewrites its end vectors: with one
-    // chunk per contig, or boundaries that were already exact, the quiet pass IS that re-run pass)
-    const int want = std::min(max_pass, std::max(ss_pass0 + (last_ss_passes > 0 ? last_ss_passes + (cert_launch || ss_need_cert_pass ? 1 : 0) : 6),
-                                                 std::max(ss_light_f, ss_light_b) + 2));
-    ss_launch_passes(want);
+    ss_launched = cp.pass0;
+    ss_launch_passes(cp.want);
     // (no event behind the passes here: run_chains_ss records EV_CHAINS_END at this very position, and every record costs the queue
     // ~3 us in front of the statistics' critical branch - tools/sync_lab.hip)
 }
@@ -713,8 +722,8 @@ bool smcpp_im::wait_done(int epoch) {
 
 void smcpp_im::run_chains_ss() {
     hipStream_t s = stream;
-    const int *chf = h_flags, *chb = h_flags + (max_pass + 1);
-    const int p0 = ss_pass0;
+    const int *chf = h_flags, *chb = h_flags + (plan.max_pass + 1);
+    const int p0 = chain_pass.pass0;
     auto first_quiet = [p0](const int *cf, const int *cb, int upto) {
         for (int j = p0; j < upto; ++j)
             if (cf[j] == 0 && cb[j] == 0) return j;
@@ -745,14 +754,14 @@ void smcpp_im::run_chains_ss() {
             // trajectory; a pass that stores everything always sets its flag), every chunk's input is what it last ran from and the
             // next pass would skip them all: that pass is the quiet one, without having been launched
             const int L = ss_launched - 1;
-            const int *ecf = h_flags + 2 * (max_pass + 1), *ecb = h_flags + 3 * (max_pass + 1);
+            const int *ecf = h_flags + 2 * (plan.max_pass + 1), *ecb = h_flags + 3 * (plan.max_pass + 1);
             if (ecf[L] == 0 && ecb[L] == 0) q = ss_launched;
         }
-        if (q >= 0 || ss_launched >= max_pass) break;
+        if (q >= 0 || ss_launched >= plan.max_pass) break;
         stats_enqueued = false;
         done_covers_stats = false;
         if (first_launched < 0) first_launched = ss_launched;
-        ss_launch_passes(std::min(max_pass, ss_launched + 3));
+        ss_launch_passes(std::min(plan.max_pass, ss_launched + 3));
     }
     chains_dual = false;
     if (ss_args.dbg) {
@@ -1319,15 +1328,15 @@ void smcpp_im::estep() {
     // (chains_ss.hpp: k_gamma_rows_scan); SMCPP_GAMMA_SCAN=0: eigensystems, as in rounds 1-5 (M <= 256)
     const bool gamma_scan = !opt().off(smcpp_opt::O_GAMMA_SCAN);
     const bool eigfree_static = !eigfree_off && Mp <= 1024 && ss_max_span <= 64 && (!save_gamma || gamma_scan);
-    if (Mp > 256 && !(ss_static && eigfree_static))
+    if (Mp > 256 && !(plan.scan && eigfree_static))
         throw std::runtime_error("more than 256 hidden states: only the scan chains with eigen-free statistics are built (rows longer than "
                                  "64 positions are cut into pieces at construction unless SMCPP_SPLIT_SPANS=0 / SMCPP_EIGFREE=0 forbid it or "
                                  "the pieces would not fit the device)");
     // only the lean path (scan chains + eigen-free statistics) reads a device-prepared emission table from HBM alone (its
     // underflow bound is checked by the kernel that forms the table); eigensystems, operand layouts, the dense chains and the
     // bound for longer spans need the host copy
-    if (E_on_dev && !(ss_static && eigfree_static)) sync_host_E();
-    ss_active = ss_static && ss_extract_generators();
+    if (E_on_dev && !(plan.scan && eigfree_static)) sync_host_E();
+    ss_active = plan.scan && ss_extract_generators();
     if (Mp > 256 && !ss_active)
         throw std::runtime_error("more than 256 hidden states: the transition matrix must have the structure of the reference's "
                                  "HJTransition (the dense fallback kernels stop at 256)");
@@ -1335,13 +1344,13 @@ void smcpp_im::estep() {
     if (!ss_active) ss_warm_valid = false;
     eigfree = ss_active && eigfree_static;
     if (E_on_dev && !(ss_active && eigfree)) sync_host_E();      // (a transition matrix without the structure)
-    if (ss_active && !ss_hybrid) { prepass_launched = false; static_packed = false; ss_launch_initial(); }   // the chains need no eigensystem: they start now
+    if (ss_active && !plan.hybrid) { prepass_launched = false; static_packed = false; ss_launch_initial(); }   // the chains need no eigensystem: they start now
     else if (ss_active) { prepass_launched = false; static_packed = false; }
     else stage_static_and_prepass();   // (when eligible) pass 0 of both chains starts now, on eigen-free operands
     tr.mark("estep: first launches");
     host_prep_and_upload();   // the reference rebuilds the eigensystems on every E-step (inference_manager.cpp:112)
     tr.mark("estep: host_prep_and_upload");
-    if (ss_active && ss_hybrid) ss_launch_initial();       // hybrid rows read the eigensystems: the chains start behind them
+    if (ss_active && plan.hybrid) ss_launch_initial();       // hybrid rows read the eigensystems: the chains start behind them
     auto t1 = std::chrono::steady_clock::now();
     if (ss_active) run_chains_ss(); else run_chains();
     tr.mark("estep: chains (host view)");

@@ -155,22 +155,6 @@ int smcpp_rccl_fetch(smcpp_im *im, double *out, long n) {
     API_END
 }
 
-int smcpp_set_chunking(smcpp_im *im, int rows_per_chunk, double eps_alpha, double eps_beta) {
-    API_BEGIN
-    HIPCHK(hipSetDevice(im->device));
-    if (eps_alpha > 0) im->eps_f = (float)eps_alpha;
-    if (eps_beta > 0) im->eps_b = eps_beta;
-    if (rows_per_chunk != im->user_rows_per_chunk) {
-        im->user_rows_per_chunk = rows_per_chunk;
-        im->warm_valid = false;
-        im->make_chunks();
-        im->upload_chunk_state();
-        im->setup_power();
-        im->last_fwd_passes = im->last_bwd_passes = 0;
-    }
-    API_END
-}
-
 int smcpp_last_timing(smcpp_im *im, double out[9]) {
     API_BEGIN im->resolve_timing(); std::memcpy(out, im->timing, sizeof(double) * 9); API_END
 }
@@ -180,115 +164,6 @@ int smcpp_last_host_timing(smcpp_im *im, double out[4]) {
 }
 
 void *smcpp_stream(smcpp_im *im) { return (void *)im->stream; }
-
-// which chain kernels this manager runs: 2 cooperative, 3 cooperative with streamed operands,
-// 4 lock-step on the matrix cores (chosen at construction / smcpp_set_chunking from the state count and the input size)
-// 5 = scans over the semiseparable structure of T (chains_ss.hpp; the dense kernels named by the other values remain the
-// fallback of an E-step whose T has no such structure)
-int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *rows, long long nslots, long long floor_cost, int *out) {
-    API_BEGIN
-    if (n_contigs <= 0 || nslots <= 0) throw std::runtime_error("smcpp_host_chunk_counts: empty input");
-    const std::vector<long long> c(cost, cost + n_contigs);
-    const std::vector<int> r(rows, rows + n_contigs);
-    const std::vector<int> ncs = ss_chunk_counts(c, r, nslots, floor_cost);
-    std::copy(ncs.begin(), ncs.end(), out);
-    API_END
-}
-
-int smcpp_chain_mode(smcpp_im *im) { return im ? (im->ss_static ? (im->ss_hybrid ? 6 : 5) : im->chain_mode) : -1; }
-
-// Test hook (tests/test_gpu_seams.py): the chunk list of one direction as make_chunks left it, (contig, r0, r1, h0, h1) per chunk.
-int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out) {
-    if (!im) return -1;
-    const std::vector<Chunk> &v = backward ? im->chunks_b : im->chunks;
-    for (size_t j = 0; j < v.size() && (long long)j < (long long)cap && out; ++j) {
-        const Chunk &ch = v[j];
-        const int t[5] = {ch.contig, ch.r0, ch.r1, ch.h0, ch.h1};
-        std::copy(t, t + 5, out + 5 * j);
-    }
-    return (int)v.size();
-}
-
-// Every SMCPP_* switch is parsed once per process (engine_options.hpp); this re-reads the environment.
-void smcpp_reload_options(void) { smcpp_opt::reload(); }
-
-// One JSON object: the switches found in the environment and the plan this manager resolved from them and from its input (chain
-// family, states per lane, chunk counts, history passes, arithmetic of the stored passes and the statistics plan of the LAST
-// E-step).  Returns the length the text needs (without the terminating zero); writes at most cap - 1 characters.
-int smcpp_describe(smcpp_im *im, char *buf, int cap) {
-    std::string s = "{";
-    s += smcpp_opt::describe_options();
-    if (im) {
-        char t[1024];
-        const int fam = im->ss_static ? (im->ss_hybrid ? 6 : 5) : im->chain_mode;
-        snprintf(t, sizeof t,
-                 ", \"plan\": {\"chain_family\": %d, \"scan_chains\": %s, \"hybrid_rows\": %s, \"states\": %d, \"states_padded\": %d, "
-                 "\"states_per_lane\": %d, \"keys\": %d, \"eigen_keys\": %d, \"rows\": %lld, \"positions\": %lld, \"max_span\": %d, "
-                 "\"chunks_forward\": %zu, \"chunks_backward\": %zu, \"wavefronts_per_simd\": %d, \"halo_pass\": %s, "
-                 "\"light_passes_forward\": %d, \"light_passes_backward\": %d, \"float_scans_in_stored_passes\": %s, \"two_row_scans\": %s, "
-                 "\"passes_to_certificate\": %d, \"passes_launched\": %d, \"certificate_pass_launched_up_front\": %s, "
-                 "\"save_gamma\": %s, \"eigen_free_statistics\": %s, \"per_row_gamma\": \"%s\", \"long_rows_cut\": %s, \"warm_start\": %s, \"host_threads\": %d",
-                 fam, im->ss_static ? "true" : "false", im->ss_hybrid ? "true" : "false", im->M, im->Mp, im->NPL, im->K, im->Ke,
-                 (long long)(im->total_rows - im->n_contigs), (long long)im->ss_positions, im->ss_max_span, im->chunks.size(),
-                 im->chunks_b.size(), im->ss_wpc, (im->ss_static && im->ss_args.halo) ? "true" : "false", im->ss_light_f, im->ss_light_b,
-                 (im->ss_static && im->ss_args.mixed) ? "true" : "false",
-                 (im->ss_static && ss_two_row_scans(im->NPL, im->ss_hybrid, im->K, im->ss_nlds, im->Mp)) ? "true" : "false", im->last_ss_passes, im->ss_launched,
-                 (opt().on(smcpp_opt::O_SS_CERT_PASS) || im->ss_need_cert_pass) ? "true" : "false", im->save_gamma ? "true" : "false",
-                 im->eigfree ? "true" : "false", !im->save_gamma ? "none" : im->eigfree ? "scan steps" : im->stats_plan.gamma_form == StatsPlan::GAMMA_PIECES ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
-                 im->warm_start ? "true" : "false", omp_get_max_threads());
-        s += t;
-        {
-            // power jumps of the scan chains: `eligible` is the manager's decision (input, state count, SMCPP_SS_JUMP), `run` whether the
-            // last E-step's launches jumped; key = index into the caller's key list, -1 = none
-            const bool el = im->ss_jump_on();
-            snprintf(t, sizeof t, ", \"power_jumps\": {\"eligible\": %s, \"run\": %s, \"key\": %d, \"key_slot\": %d, \"powers\": [%s]}}",
-                     el ? "true" : "false", im->ss_jump_launch ? "true" : "false", el ? im->ss_jump_kid : -1,
-                     el && !im->ss_slot_of_key.empty() ? im->ss_slot_of_key[im->ss_jump_kid] : -1, el ? std::to_string(im->ss_jump_P).c_str() : "");
-            s += t;
-        }
-        // the statistics plan of the last E-step (null before the first one): the stream of every branch, the form of every kernel family
-        const StatsPlan &p = im->stats_plan;
-        static const char *const stream[] = {"main", "second", "third", "high priority"}, *const rank[] = {"per slab", "teams", "wide"};
-        static const char *const eigen[] = {"none", "fold on the scans", "fold on the matrix cores", "generation 2", "classic"};
-        static const char *const gsum[] = {"one pass", "own stream", "span > 1 tail", "span-1 branch"};
-        static const char *const gamma[] = {"none", "scan steps", "eigen-power pieces + scan steps", "eigensystem batches", "eigensystem rows"};
-        snprintf(t, sizeof t,
-                 ", \"statistics\": {\"span_gt1_stream\": \"%s\", \"span1_stream\": \"%s\", \"gamma_sums_stream\": \"%s\", "
-                 "\"loglik_stream\": \"%s\", \"per_row_gamma_stream\": \"%s\", \"span1_form\": \"%s\", \"rank_update\": \"%s\", "
-                 "\"eigen\": \"%s\", \"span_gt1_rank_early\": %s, \"gamma_sums_reduced\": \"%s\", \"per_row_gamma\": \"%s\", "
-                 "\"per_row_gamma_beside\": %s, \"slab_rows_span1\": %d, \"slab_rows_span_gt1\": %d, \"reduction_shares\": %d}",
-                 stream[p.span_gt1], stream[p.span1], stream[p.gsum], stream[p.loglik], stream[p.gamma], p.s1_one_pass ? "one pass" : "two kernels",
-                 rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false",
-                 im->slab_rows_1, im->slab_rows_e, im->ZS);
-        s += p.resolved ? t : ", \"statistics\": null";
-        // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
-        static const char *const route[] = {"none", "device", "host"};
-        s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";
-        // the launch shape of the last posterior path call - paths per wavefront, batches, wavefronts - and the wavefronts of the
-        // last posterior transition call (0: none yet); a wavefront takes more than one batch / row where there are fewer of them
-        s += ", \"path_batch\": " + std::to_string(im->pp_batch) + ", \"path_batches\": " + std::to_string(im->pp_batches);
-        s += ", \"path_waves\": " + std::to_string(im->pp_waves) + ", \"transition_waves\": " + std::to_string(im->pt_waves);
-        // ... and of the last posterior position call: its wavefronts and the engine rows it walked
-        s += ", \"position_waves\": " + std::to_string(im->pq_waves) + ", \"position_rows_walked\": " + std::to_string(im->pq_walked);
-        // ... and of the last simulate call: its wavefronts, its (contig, replicate) pairs and the loud positions it wrote
-        s += ", \"simulate_waves\": " + std::to_string(im->sim_waves) + ", \"simulate_units\": " + std::to_string(im->sim_units);
-        s += ", \"simulate_events\": " + std::to_string(im->sim_events);
-        // ... and of the last log-likelihood track call: the engine rows it walked, its wavefronts and how far the walk of a row
-        // from the stored float vector moved the row's evidence at worst, |A_span / log c_r - 1|
-        snprintf(t, sizeof t, ", \"ll_items\": %lld, \"ll_waves\": %d, \"ll_walk_worst_ratio\": %.6g", im->ll_nitems, im->ll_waves, im->ll_worst);
-        s += t;
-        // ... and of the last score track call: the engine rows it walked, its wavefronts and where a block's vectors are parked
-        s += ", \"score_items\": " + std::to_string(im->sc_items) + ", \"score_waves\": " + std::to_string(im->sc_waves);
-        s += ", \"score_park\": \"lds\"";
-    }
-    s += "}";
-    if (buf && cap > 0) {
-        const size_t n = std::min(s.size(), (size_t)cap - 1);
-        std::memcpy(buf, s.data(), n);
-        buf[n] = 0;
-    }
-    return (int)s.size();
-}
 
 // Test hook (tests/test_gpu_ss.py, tests/test_gpu_ss_step.py): one position of both scan chains on nvec vectors, out_f = e o (T^T x),
 // out_b = T (e o x); x, e and the outputs are [nvec][M].  Returns 2 when T has no semiseparable structure.  `form` picks the compiled
