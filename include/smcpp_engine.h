@@ -187,6 +187,12 @@ int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *row
 int smcpp_host_chain_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs,
                           int n_hs, const double *hs, int compute_units, int rows_per_chunk,
                           char *json, int json_cap, int *chunks_fwd, int *chunks_bwd, int chunk_cap, int *lengths);
+/* Host-only (no device needed, none touched): the plan of the parameter phase - which preparation runs and why - that a manager in
+ * this state resolves under the switches of the environment, as {"parameters": {...}} of smcpp_describe.  n: sample size of
+ * population 1, pieces_plus_states: model pieces + hidden-state boundaries (what the device preparation's size limit is asked).
+ * Writes at most json_cap - 1 characters; *length: what the text needs (call with json_cap 0 to size the buffer). */
+int smcpp_host_param_plan(int npop, int have_raw, int force_host, int nder, int n, int pieces_plus_states, int have_global,
+                          char *json, int json_cap, int *length);
 int smcpp_chain_mode(smcpp_im *im);
 /* diagnostics (host only): the chunk list of the scan chains as the last plan cut it - backward == 0: the forward chain's, else the
  * backward chain's (the two directions have lists of their own).  Writes up to `cap` chunks into out[5 * cap] as (contig, r0, r1, h0,

@@ -97,6 +97,18 @@ def host_chain_plan(n, na, contigs, hs, compute_units, rows_per_chunk=0):
     return json.loads(buf.value.decode()), fwd[:need[1]], bwd[:need[2]]
 
 
+def host_param_plan(npop=1, have_raw=False, force_host=False, nder=0, n=4, pieces_plus_states=33, have_global=False):
+    """The "parameters" object of describe() for a manager in this state under the switches of the environment, without a device
+    (`smcpp_host_param_plan`); the entries an E-step or a getter changes are as a fresh manager has them."""
+    import json
+    args = (int(npop), int(bool(have_raw)), int(bool(force_host)), int(nder), int(n), int(pieces_plus_states), int(bool(have_global)))
+    need = C.c_int(0)
+    check(lib().smcpp_host_param_plan(*args, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value + 1)
+    check(lib().smcpp_host_param_plan(*args, buf, need.value + 1, C.byref(need)))
+    return json.loads(buf.value.decode())["parameters"]
+
+
 def host_eigensystem(A):
     A = np.ascontiguousarray(A, dtype=np.float64)
     n = A.shape[0]

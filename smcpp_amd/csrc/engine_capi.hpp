@@ -33,9 +33,9 @@ int smcpp_create_twopop(int n1, int n2, int a1, int a2, int n_contigs, const int
 int smcpp_rccl_destroy(smcpp_im *im);
 void smcpp_destroy(smcpp_im *im) { if (im && im->rccl) (void)smcpp_rccl_destroy(im); delete im; }
 
-int smcpp_set_theta(smcpp_im *im, double v) { API_BEGIN im->params_fresh = false; im->theta = v; im->dirty = true; if (im->have_model) im->have_raw = false; API_END }
-int smcpp_set_rho(smcpp_im *im, double v) { API_BEGIN im->params_fresh = false; im->rho = v; im->dirty = true; if (im->have_model) im->have_raw = false; API_END }
-int smcpp_set_alpha(smcpp_im *im, double v) { API_BEGIN im->params_fresh = false; im->alpha = v; im->dirty = true; if (im->have_model) im->have_raw = false; API_END }
+int smcpp_set_theta(smcpp_im *im, double v) { API_BEGIN im->theta = v; im->params_changed(true); API_END }
+int smcpp_set_rho(smcpp_im *im, double v) { API_BEGIN im->rho = v; im->params_changed(true); API_END }
+int smcpp_set_alpha(smcpp_im *im, double v) { API_BEGIN im->alpha = v; im->params_changed(true); API_END }
 
 int smcpp_set_params(smcpp_im *im, int K, const double *a, const double *da, int nder, const double *s) {
     API_BEGIN
@@ -48,10 +48,8 @@ int smcpp_set_params(smcpp_im *im, int K, const double *a, const double *da, int
     im->nder = (da && nder > 0) ? nder : 0;
     im->model_da.clear();
     if (im->nder) im->model_da.assign(da, da + (size_t)K * nder);
-    im->params_fresh = false;
     im->have_model = true;
-    im->have_raw = false;
-    im->dirty = true;
+    im->params_changed(true);
     API_END
 }
 
@@ -79,18 +77,15 @@ int smcpp_set_params_twopop(smcpp_im *im, int Kd, const double *ad, const double
         if (da1) im->model_da1.assign(da1, da1 + (size_t)K1 * nder);
         if (da2) im->model_da2.assign(da2, da2 + (size_t)K2 * nder);
     }
-    im->params_fresh = false;
     im->have_model = true;
-    im->have_raw = false;
-    im->dirty = true;
+    im->params_changed(true);
     API_END
 }
 
 int smcpp_set_prep_mode(smcpp_im *im, int host) {
     API_BEGIN
     im->force_host_prep = host != 0;
-    im->params_fresh = false;
-    im->dirty = true;
+    im->params_changed(false);
     API_END
 }
 
@@ -119,10 +114,10 @@ int smcpp_set_raw(smcpp_im *im, const double *pi, const double *T, int K, const 
     im->raw_keys.assign(keys, keys + (size_t)K * kl);
     im->raw_E.assign(E, E + (size_t)K * M);
     im->have_raw = true;
-    im->E_on_dev = false;
-    im->tgen_valid = false; im->dT_valid = true; im->T_lazy = false;
+    im->params_on_host_route();
     im->dirty = true;
     im->nder = 0;
+    im->param_plan = im->resolve_param_plan();
     API_END
 }
 
@@ -268,9 +263,7 @@ int smcpp_set_hidden_states(smcpp_im *im, int n_hs, const double *hs) {
     im->twopop_prep.reset();
     if (!im->estep_done) im->stats_on_host = false;
     if (im->qdev) im->qdev->stats_ready = false;      // the pre-E-step statistics are span_sum * pi_default: restage them
-    im->dirty = true;
-    im->params_fresh = false;
-    if (im->have_model) im->have_raw = false;
+    im->params_changed(true);
     API_END
 }
 int smcpp_get_keys(smcpp_im *im, int *keys) {
@@ -407,8 +400,8 @@ int smcpp_set_global_keys(smcpp_im *im, int Kg, const int *gkeys) {
     im->pack_tables_ready = false;
     if (im->dprep) im->dprep->keys_ready = false;
     if (im->qdev) im->qdev->stats_ready = false;
-    im->E_on_dev = false;
-    im->params_fresh = false;              // the emission table is now prepared over the global key list
+    im->E_on_dev = false;                  // (the device's table is dropped, not fetched; the rest of the residency state stands)
+    im->params_changed(false, false);      // the emission table is now prepared over the global key list
     im->Eg.clear(); im->dEg.clear();
     API_END
 }
@@ -540,7 +533,7 @@ static std::string describe_chain_plan(const smcpp_im *im) {
              (p.scan && cp.mixed) ? "true" : "false", (p.scan && p.two_row_scans) ? "true" : "false", im->last_ss_passes, im->ss_launched,
              // (the switch and the learned flag as they stand now, not as the last E-step found them)
              im->resolve_chain_pass().cert_up_front ? "true" : "false", im->save_gamma ? "true" : "false",
-             im->eigfree ? "true" : "false", !im->save_gamma ? "none" : im->eigfree ? "scan steps" : im->stats_plan.gamma_form == StatsPlan::GAMMA_PIECES ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
+             im->estep_route.eigfree ? "true" : "false", !im->save_gamma ? "none" : im->estep_route.eigfree ? "scan steps" : im->stats_plan.gamma_form == StatsPlan::GAMMA_PIECES ? "eigen-power pieces + scan steps" : "eigensystem", im->split_spans ? "true" : "false",
              im->warm_start ? "true" : "false", omp_get_max_threads());
     s += t;
     // power jumps of the scan chains: `eligible` is the manager's decision (input, state count, SMCPP_SS_JUMP), `run` whether the
@@ -550,6 +543,19 @@ static std::string describe_chain_plan(const smcpp_im *im) {
              el ? "true" : "false", cp.jump ? "true" : "false", el ? p.jump_kid : -1,
              el && !im->ss_slot_of_key.empty() ? im->ss_slot_of_key[p.jump_kid] : -1, el ? std::to_string(p.jump_P).c_str() : "");
     return s + t;
+}
+
+// "parameters" of smcpp_describe: the plan of the last prepare_params() / set_raw, where the tables live NOW, the last E-step's route
+static std::string describe_param_plan(const smcpp_im *im) {
+    static const char *const source[] = {"", "RAW", "ONEPOP_HOST", "ONEPOP_DEVICE", "TWOPOP_HOST", "TWOPOP_DEVICE_BATCH"};
+    static const char *const why[] = {"none", "switch", "prep mode", "size not supported", "literal CSFS", "derivative seeds (two populations)"};
+    const ParamPlan &p = im->param_plan;
+    const bool seeds = !im->have_raw && im->nder > 0; char t[512];
+    snprintf(t, sizeof t, ", \"parameters\": {\"source\": \"%s\", \"why_host\": \"%s\", \"emission_table\": \"%s\", \"transition\": \"%s\", "
+             "\"transition_jacobian\": \"%s\", \"key_list\": \"%s\", \"eigen_free_statistics\": %s, \"lean\": %s}", source[p.source], why[p.why_host], im->E_on_dev ? "device" : "host",
+             im->T_lazy ? "generators" : "expanded", !seeds ? "none" : im->dT_valid ? "expanded" : "planes", p.global_keys ? "global" : "local",
+             im->estep_route.eigfree ? "true" : "false", im->estep_route.eigfree ? "true" : "false");       // (lean = eigen-free statistics on the scan chains)
+    return p.source != ParamPlan::NONE ? t : ", \"parameters\": null";
 }
 
 // One JSON object: the switches found in the environment and the plan this manager resolved from them and from its input (chain
@@ -579,6 +585,7 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
         static const char *const route[] = {"none", "device", "host"};
         s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";
+        s += describe_param_plan(im);
         // the launch shape of the last posterior path call - paths per wavefront, batches, wavefronts - and the wavefronts of the
         // last posterior transition call (0: none yet); a wavefront takes more than one batch / row where there are fewer of them
         s += ", \"path_batch\": " + std::to_string(im->pp_batch) + ", \"path_batches\": " + std::to_string(im->pp_batches);

@@ -386,4 +386,16 @@ int smcpp_host_chain_plan(int npop, const int *n, const int *na, int n_contigs, 
     API_END
 }
 
+// resolve_param_plan on a manager that exists on the host only, printed as smcpp_describe prints it (include/smcpp_engine.h)
+int smcpp_host_param_plan(int npop, int have_raw, int force_host, int nder, int n, int pieces_plus_states, int have_global, char *json, int json_cap, int *length) {
+    API_BEGIN
+    smcpp_im im;                                                       // (hs stays empty: the sum is what counts)
+    im.npop = npop; im.have_raw = have_raw != 0; im.force_host_prep = force_host != 0; im.nder = nder; im.n[0] = n; im.have_global = have_global != 0;
+    im.model.a.assign(std::max(0, pieces_plus_states), 1.0); im.param_plan = im.resolve_param_plan();
+    const std::string s = "{" + describe_param_plan(&im).substr(2) + "}";
+    if (json && json_cap > 0) snprintf(json, (size_t)json_cap, "%s", s.c_str());
+    if (length) *length = (int)s.size();
+    API_END
+}
+
 }  // extern "C"

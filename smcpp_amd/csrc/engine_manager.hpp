@@ -80,6 +80,19 @@ struct ChainPass {
     int want_f = 0, want_b = 0, prio = 1, prio_mask = 7;
 };
 
+// Where pi / T / E come from, per prepare_params() call (resolve_param_plan: no write, no HIP call).  DESIGN.md section 5: field, decided from, switch.
+struct ParamPlan {
+    enum Source { NONE, RAW, ONEPOP_HOST, ONEPOP_DEVICE, TWOPOP_HOST, TWOPOP_DEVICE_BATCH } source = NONE;      // NONE: nothing prepared yet
+    enum WhyHost { NOT_FORCED, SWITCH, PREP_MODE, SIZE, LITERAL_CSFS, SEEDS_TWOPOP } why_host = NOT_FORCED;     // the FIRST condition that forced the host
+    bool global_keys = false, lazy_T = false, q_device_allowed = true;
+};
+
+// What an E-step decides from where the parameters live (resolve_estep_route).  eigfree: the lean E-step; host_E: the device's table comes back first
+struct EstepRoute {
+    bool eigfree_static = false, ss_active = false, eigfree = false, arena_side = false, host_E = false;
+    const char *refuse = nullptr;
+};
+
 struct smcpp_im {
     // ---- static problem description -------------------------------------------------------------------------
     int npop = 1, keylen = 3, M = 0, Mp = 0, NPL = 1, NT = 1, n_contigs = 0, K = 0, G = 0, Ke = 0;
@@ -133,6 +146,8 @@ struct smcpp_im {
     // ---- parameters -------------------------------------------------------------------------------------------
     double theta = NAN, rho = NAN, alpha = 1.0;
     bool have_raw = false, dirty = true, params_fresh = false;
+    // a setter: the prepared tables go; results_stale: so do the last E-step's vectors; model_setter: a manager with a model leaves the raw path
+    void params_changed(bool model_setter, bool results_stale = true) { params_fresh = false; dirty = dirty || results_stale; have_raw = have_raw && !(model_setter && have_model); }
     std::vector<double> pi, T, E;          // [M], [M*M], [K*M]
     smcpp_host::ModelParams model;         // a, s (for set_params); the distinguished model of a two-population manager
     smcpp_host::ModelParams model_p1, model_p2;          // two populations: per-population pieces (set_params_twopop)
@@ -181,8 +196,13 @@ struct smcpp_im {
     // vectors E / dE / emission / Eg are stale until sync_host_E() fetches them (getters, non-lean E-steps)
     std::unique_ptr<DevPrep> dprep;
     bool E_on_dev = false, force_host_prep = false;
-    void dev_prepare();
+    ParamPlan param_plan; EstepRoute estep_route;         // of the last prepare_params() / set_raw; of the last E-step (smcpp_describe: "parameters")
+    ParamPlan resolve_param_plan() const;
+    EstepRoute resolve_estep_route(bool structured_T) const;
+    void dev_prepare(const std::vector<int> &pk, int Kp_);     // (the prepared key list: global or this rank's)
     void sync_host_E();
+    void fetch_prepared_table(std::vector<double> &E_out, std::vector<double> &dE_out, bool whole);     // the device's table -> host (whole: + emission, Eg / dEg)
+    void scatter_prepared_table(std::vector<double> &Ep, std::vector<double> &dEp, std::vector<double> &E_out, std::vector<double> &dE_out, bool keep_global);
     // Q and its gradient on the device (prep_dev.hpp: k_q_reduce): the O(M) generators of the transition matrix with their
     // derivative planes (host, prep.hpp: transition_generators_jac; dT is expanded on the host only when its getter asks)
     smcpp_host::TransitionGenJac tgen;
@@ -197,6 +217,8 @@ struct smcpp_im {
     // on the same generators, bit for bit, whoever read T in between (the generators extracted back from the expanded matrix differ
     // from them in the last bits)
     bool T_from_gen = false;
+    // host preparations, set_raw.  T_from_gen is left standing: tgen_valid == false disarms its one reader (ss_extract_generators)
+    void params_on_host_route() { E_on_dev = false; tgen_valid = false; dT_valid = true; T_lazy = false; }
     smcpp_host::TransitionGenerators<double> tgen_g;
     void ensure_T() { if (T_lazy) { T = smcpp_host::transition_expand<double>(tgen_g); T_lazy = false; } }
     struct QDev {
@@ -234,8 +256,6 @@ struct smcpp_im {
     DevBuf<double> d_jdiag;                // [64] its diagonal
     // LDS the hybrid rows' eigenvector tables take (+ one scratch vector per wavefront)
     static size_t ss_tab_bytes(const ChainPlan &p, int Mp) { return p.hybrid ? ((size_t)p.nk_lds * (p.dirsplit() ? 2 : 4) * Mp * (Mp + 1) + 8 * 64) * sizeof(double) : 0; }
-    bool ss_active = false;                // this E-step's chains run on the scan kernels
-    bool eigfree = false;                  // ... and its statistics need no eigensystem either (k_span_fold): no eigensolve at all
     int ss_max_span = 0;                   // the longest row (build_layout)
     // what run_chains_ss learns (state, not plan)
     int ss_launched = 0, last_ss_passes = 0;
@@ -244,8 +264,6 @@ struct smcpp_im {
     // vector the PREVIOUS converged E-step left (parity ss_warm_parity of the end-vector arrays) instead of pi / the uniform
     // vector, and one light pass fewer runs; pass indices then start at ChainPass::pass0 (1 or 2: the parity the first pass reads)
     bool ss_warm_valid = false;
-    // lean E-steps copy the (small) parameter arena on stream2 while the chains run; the statistics wait for EV_ARENA
-    bool arena_side = false;
     int ss_warm_parity = 0;
     std::vector<int> ss_slot_of_key;       // frequency rank of every key (slot 0 = most rows)
     DevBuf<int2> d_rowdesc_ss;             // [rows, padded] {key slot, span}

@@ -24,16 +24,60 @@ static void split_duals(const std::vector<smcpp_host::dual> &x, int nder, std::v
     }
 }
 
+// The route of this prepare_params() call; why_host names the FIRST host condition: switch, prep mode, then size, literal CSFS / seeds
+ParamPlan smcpp_im::resolve_param_plan() const {
+    typedef ParamPlan P; P p;
+    p.source = P::RAW; p.global_keys = have_global; p.q_device_allowed = !opt().is(smcpp_opt::O_Q, "host");
+    if (have_raw) return p;
+    p.why_host = opt().is(smcpp_opt::O_PREP, "host") ? P::SWITCH : force_host_prep ? P::PREP_MODE
+                 : npop == 2 ? (nder > 0 ? P::SEEDS_TWOPOP : P::NOT_FORCED)
+                 : !DevPrep::supported(n[0], (int)model.a.size() + (int)hs.size()) ? P::SIZE : smcpp_host::csfs_direct_flag() ? P::LITERAL_CSFS : P::NOT_FORCED;
+    const bool dev = p.why_host == P::NOT_FORCED;
+    p.source = npop == 2 ? (dev ? P::TWOPOP_DEVICE_BATCH : P::TWOPOP_HOST) : (dev ? P::ONEPOP_DEVICE : P::ONEPOP_HOST);
+    p.lazy_T = p.source == P::ONEPOP_DEVICE && nder == 0 && !opt().off(smcpp_opt::O_T_LAZY);
+    return p;
+}
+
+void smcpp_im::scatter_prepared_table(std::vector<double> &Ep, std::vector<double> &dEp, std::vector<double> &E_out, std::vector<double> &dE_out, bool keep_global) {
+    if (!have_global) { E_out.swap(Ep); dE_out.swap(dEp); return; }
+    E_out.assign((size_t)K * M, 0.0);
+    dE_out.assign(nder > 0 ? (size_t)K * M * nder : 0, 0.0);
+    for (int k = 0; k < K; ++k) {
+        const int kg = local_to_global[k];
+        std::memcpy(&E_out[(size_t)k * M], &Ep[(size_t)kg * M], sizeof(double) * M);
+        if (nder > 0) std::memcpy(&dE_out[(size_t)k * M * nder], &dEp[(size_t)kg * M * nder], sizeof(double) * M * nder);
+    }
+    if (keep_global) { Eg.swap(Ep); dEg.swap(dEp); }
+}
+
 void smcpp_im::prepare_params() {
     // do_dirty_work (inference_manager.cpp:213-229) for the model-parameter path; the raw path already has pi/T/E.
     if (have_raw || params_fresh) return;
     if (!have_model) throw std::runtime_error("no model parameters: call set_params or set_raw before E_step");
     if (std::isnan(theta) || std::isnan(rho)) throw std::runtime_error("theta / rho / alpha must be set");
-    if (npop == 2) {
-        // TwoPopInferenceManager::setParams (inference_manager.cpp:542-550): pi / T from the distinguished model,
-        // emissions from the joint CSFS of (population 1, population 2, split)
-        if (model_p1.a.empty() || model_p2.a.empty())
-            throw std::runtime_error("two-population manager: call set_params_twopop (or set_raw) before E_step");
+    if (npop == 2 && (model_p1.a.empty() || model_p2.a.empty()))
+        throw std::runtime_error("two-population manager: call set_params_twopop (or set_raw) before E_step");
+    typedef ParamPlan P;
+    const P &pp = param_plan = resolve_param_plan();
+    // with a global key dictionary (multi-GPU) the table is prepared for EVERY global key (Q on all-reduced statistics); the local one is a sub-list
+    const std::vector<int> &pk = pp.global_keys ? gkeys : keys;
+    const int Kp_ = (int)(pk.size() / keylen);
+    std::vector<double> Ep, dEp;
+    switch (pp.source) {
+    default: return;                       // (RAW: returned above)
+    case P::ONEPOP_DEVICE: case P::ONEPOP_HOST:
+        // (kept across E-steps: it caches the keys' marginalisation bins; rebuilt when the hidden states change)
+        if (!prep1 || prep1_hs != hs) {
+            prep1.reset(new smcpp_host::OnePopPrep(n[0], hs, polarization_error)); prep1_hs = hs;
+            if (dprep) dprep->keys_ready = false;
+        }
+        if (pp.source == P::ONEPOP_DEVICE) { dev_prepare(pk, Kp_); break; }      // conditioned SFS + emission table on the device
+        params_on_host_route();
+        if (nder > 0) prep1->compute_with_jacobian(model, model_da, nder, theta, rho, alpha, pk, Kp_, pi, T, Ep, dpi, dT, dEp, &emission, &demission);
+        else { prep1->compute(model, theta, rho, alpha, pk, Kp_, pi, T, Ep, &emission); demission.clear(); }
+        break;
+    case P::TWOPOP_DEVICE_BATCH: case P::TWOPOP_HOST:
+        // TwoPopInferenceManager::setParams (inference_manager.cpp:542-550): joint CSFS; its two batched conditioned SFS on the device (values only)
         if (!twopop_prep) {
             twopop_prep.reset(new smcpp_host::TwoPopPrep(n[0], n[1], na[0], na[1], hs, polarization_error));
             // The two-population preparation is the one host phase that still runs on a team of threads, in two parallel regions per
@@ -44,80 +88,26 @@ void smcpp_im::prepare_params() {
             // at 800 - 825).  SMCPP_OMP_BLOCKTIME overrides.
             if (kmp_set_blocktime && !opt().has(smcpp_opt::O_OMP_BLOCKTIME)) kmp_set_blocktime(2);
         }
-        smcpp_host::TwoPopPrep &prep = *twopop_prep;
-        {
-            // the batched conditioned SFS on the device (values; SMCPP_PREP=host / smcpp_set_prep_mode(1): everything on the host)
-            const bool host_only2 = opt().is(smcpp_opt::O_PREP, "host");
-            if (!twopop_dev) { twopop_dev.reset(new TwoPopDevCsfs()); twopop_dev->device = device; twopop_dev->stream = stream; }
-            prep.batch_dev = (host_only2 || force_host_prep || nder > 0) ? nullptr : twopop_dev.get();
-        }
-        E_on_dev = false;
-        tgen_valid = false; dT_valid = true; T_lazy = false;
-        // with a global key dictionary (multi-GPU) the table is prepared for EVERY global key - Q on the all-reduced statistics
-        // also covers keys only other ranks' contigs hold; the local table is the sub-list of this rank's keys
-        const std::vector<int> &pk2 = have_global ? gkeys : keys;
-        const int K2 = (int)(pk2.size() / keylen);
-        std::vector<double> Ep, dEp;
+        if (!twopop_dev) { twopop_dev.reset(new TwoPopDevCsfs()); twopop_dev->device = device; twopop_dev->stream = stream; }
+        twopop_prep->batch_dev = pp.source == P::TWOPOP_DEVICE_BATCH ? twopop_dev.get() : nullptr;
+        params_on_host_route();
         if (nder > 0) {
             smcpp_host::DualScope sc(nder);
             std::vector<smcpp_host::dual> pd, Td, Ed, emd;
-            prep.compute_t<smcpp_host::dual>(make_dual_model(model, model_da, nder), make_dual_model(model_p1, model_da1, nder),
-                                             make_dual_model(model_p2, model_da2, nder), split, theta, rho, alpha, pk2, K2,
-                                             pd, Td, Ed, &emd);
+            twopop_prep->compute_t<smcpp_host::dual>(make_dual_model(model, model_da, nder), make_dual_model(model_p1, model_da1, nder),
+                                                     make_dual_model(model_p2, model_da2, nder), split, theta, rho, alpha, pk, Kp_, pd, Td, Ed, &emd);
             split_duals(pd, nder, pi, dpi); split_duals(Td, nder, T, dT); split_duals(Ed, nder, Ep, dEp);
             split_duals(emd, nder, emission, demission);
         } else {
             smcpp_host::ModelParamsT<double> d, p1, p2;
             d.a = model.a; d.s = model.s; p1.a = model_p1.a; p1.s = model_p1.s; p2.a = model_p2.a; p2.s = model_p2.s;
-            prep.compute_t<double>(d, p1, p2, split, theta, rho, alpha, pk2, K2, pi, T, Ep, &emission);
+            twopop_prep->compute_t<double>(d, p1, p2, split, theta, rho, alpha, pk, Kp_, pi, T, Ep, &emission);
             demission.clear();
         }
-        if (!have_global) { E.swap(Ep); dE.swap(dEp); Eg.clear(); dEg.clear(); }
-        else {
-            E.assign((size_t)K * M, 0.0);
-            dE.assign(nder > 0 ? (size_t)K * M * nder : 0, 0.0);
-            for (int k = 0; k < K; ++k) {
-                const int kg = local_to_global[k];
-                std::memcpy(&E[(size_t)k * M], &Ep[(size_t)kg * M], sizeof(double) * M);
-                if (nder > 0) std::memcpy(&dE[(size_t)k * M * nder], &dEp[(size_t)kg * M * nder], sizeof(double) * M * nder);
-            }
-            Eg.swap(Ep); dEg.swap(dEp);
-        }
-        params_fresh = true;
-        return;
+        if (!have_global) { Eg.clear(); dEg.clear(); }               // (the one-population host route leaves them standing)
+        break;
     }
-    // (kept across E-steps: it caches the keys' marginalisation bins; rebuilt when the hidden states change)
-    if (!prep1 || prep1_hs != hs) {
-        prep1.reset(new smcpp_host::OnePopPrep(n[0], hs, polarization_error)); prep1_hs = hs;
-        if (dprep) dprep->keys_ready = false;
-    }
-    smcpp_host::OnePopPrep &prep = *prep1;
-    {
-        // conditioned SFS + emission table on the device (SMCPP_PREP=host: the host routines, as in rounds 1-3)
-        const bool host_only = opt().is(smcpp_opt::O_PREP, "host");
-        if (!host_only && !force_host_prep && DevPrep::supported(n[0], (int)model.a.size() + (int)hs.size()) && !smcpp_host::csfs_direct_flag()) { dev_prepare(); return; }
-    }
-    E_on_dev = false;
-    tgen_valid = false; dT_valid = true; T_lazy = false;
-    // with a global key dictionary (multi-GPU) the emission table is prepared for every global key; the local table
-    // is the sub-list of the keys this rank's contigs hold
-    const std::vector<int> &pk = have_global ? gkeys : keys;
-    const int Kp_ = (int)(pk.size() / keylen);
-    std::vector<double> Ep, dEp;
-    if (nder > 0) prep.compute_with_jacobian(model, model_da, nder, theta, rho, alpha, pk, Kp_, pi, T, Ep, dpi, dT, dEp,
-                                             &emission, &demission);
-    else { prep.compute(model, theta, rho, alpha, pk, Kp_, pi, T, Ep, &emission); demission.clear(); }
-    if (!have_global) { E.swap(Ep); dE.swap(dEp); }
-    else {
-        E.assign((size_t)K * M, 0.0);
-        dE.assign(nder > 0 ? (size_t)K * M * nder : 0, 0.0);
-        for (int k = 0; k < K; ++k) {
-            const int kg = local_to_global[k];
-            std::memcpy(&E[(size_t)k * M], &Ep[(size_t)kg * M], sizeof(double) * M);
-            if (nder > 0) std::memcpy(&dE[(size_t)k * M * nder], &dEp[(size_t)kg * M * nder], sizeof(double) * M * nder);
-        }
-        Eg.swap(Ep); dEg.swap(dEp);
-    }
+    if (pp.source != P::ONEPOP_DEVICE) scatter_prepared_table(Ep, dEp, E, dE, true);     // (the device route wrote its table where the kernels read it)
     params_fresh = true;
 }
 
@@ -143,11 +133,9 @@ static bool host_transition_with_planes(const smcpp_host::RateFunctionT<smcpp_ho
 
 // One-population do_dirty_work with the O(states x n^2 x directions) part on the device: the host builds the rate function
 // (O(pieces)), pi, the average coalescence times and - while the kernels already run - the transition matrix.
-void smcpp_im::dev_prepare() {
+void smcpp_im::dev_prepare(const std::vector<int> &pk, int Kp_) {
     HIPCHK(hipSetDevice(device));
     if (!dprep) { dprep.reset(new DevPrep()); dprep->set_static(prep1->tables()); }
-    const std::vector<int> &pk = have_global ? gkeys : keys;
-    const int Kp_ = (int)(pk.size() / keylen);
     if (!dprep->keys_ready) {
         // per prepared key: its row of the statistics' table, its slot of the scan chains' table, the longest span the scan
         // chains expand position by position (ss_extract_generators' underflow bound, checked by the kernel)
@@ -162,7 +150,7 @@ void smcpp_im::dev_prepare() {
         }
         dprep->set_keys(*prep1, pk, Kp_, local, slot, maxspan, K, M, Mp, plan.scan ? 64 * NPL : 0);
     }
-    T_lazy = T_from_gen = false;
+    T_lazy = T_from_gen = false;             // (both: this route sets them anew below; params_on_host_route() leaves T_from_gen alone)
     if (nder > 0) {
         HostTrace tr;
         smcpp_host::DualScope sc(nder);
@@ -200,7 +188,7 @@ void smcpp_im::dev_prepare() {
         tgen_valid = tgen.ok;
         // (the expansion waits until somebody reads the matrix - ensure_T; without usable generators, or with SMCPP_T_LAZY=0: here)
         tgen_g = std::move(g);
-        T_lazy = T_from_gen = tgen_valid && !opt().off(smcpp_opt::O_T_LAZY);
+        T_lazy = T_from_gen = tgen_valid && param_plan.lazy_T;
         if (!T_lazy) T = smcpp_host::transition_expand<double>(tgen_g);
         tr.mark("prep: T expand");
         dpi.clear(); dT.clear();
@@ -208,30 +196,17 @@ void smcpp_im::dev_prepare() {
     }
     E_on_dev = true;
     Eg.clear(); dEg.clear();
-    params_fresh = true;
 }
 
 // The emission table (and its Jacobian, and InferenceManager::emission) of a device preparation, to the host vectors
-void smcpp_im::sync_host_E() {
-    if (!E_on_dev) return;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipStreamSynchronize(stream));
-    std::vector<double> Ep, dEp;
-    dprep->fetch(Ep, dEp, emission, demission);
+void smcpp_im::fetch_prepared_table(std::vector<double> &E_out, std::vector<double> &dE_out, bool whole) {
+    HIPCHK(hipSetDevice(device)); HIPCHK(hipStreamSynchronize(stream));
+    std::vector<double> Ep, dEp, em, dem;
+    dprep->fetch(Ep, dEp, whole ? emission : em, whole ? demission : dem, whole);
     dprep->check_flags();
-    if (!have_global) { E.swap(Ep); dE.swap(dEp); }
-    else {
-        E.assign((size_t)K * M, 0.0);
-        dE.assign(nder > 0 ? (size_t)K * M * nder : 0, 0.0);
-        for (int k = 0; k < K; ++k) {
-            const int kg = local_to_global[k];
-            std::memcpy(&E[(size_t)k * M], &Ep[(size_t)kg * M], sizeof(double) * M);
-            if (nder > 0) std::memcpy(&dE[(size_t)k * M * nder], &dEp[(size_t)kg * M * nder], sizeof(double) * M * nder);
-        }
-        Eg.swap(Ep); dEg.swap(dEp);
-    }
-    E_on_dev = false;
+    scatter_prepared_table(Ep, dEp, E_out, dE_out, whole);
 }
+void smcpp_im::sync_host_E() { if (E_on_dev) { fetch_prepared_table(E, dE, true); E_on_dev = false; } }
 
 void smcpp_im::ensure_dT() {
     ensure_T();
@@ -245,8 +220,7 @@ void smcpp_im::ensure_dT() {
 // the transition matrix.  Returns false when this call has to take the host route (no device preparation, a local / global
 // key-list mismatch, the pairwise fallback of the transition matrix).
 bool smcpp_im::q_device(double val[4], double *jac) {
-    const bool off = opt().is(smcpp_opt::O_Q, "host");
-    if (off || !E_on_dev || !tgen_valid || have_raw || (have_global && !have_reduced)) return false;
+    if (!param_plan.q_device_allowed || !E_on_dev || !tgen_valid || have_raw || (have_global && !have_reduced)) return false;
     if (have_reduced && (int)g_stats.size() != 1 + M + M * M + dprep->Kk * M) return false;
     HIPCHK(hipSetDevice(device));
     if (!qdev) qdev.reset(new QDev());
@@ -391,7 +365,7 @@ void smcpp_im::host_prep_and_upload() {
     std::string err;
     // scan chains + eigen-free statistics: nothing on the device reads the float / transposed copies of T or any eigenvector
     // matrix - they are neither packed nor staged nor copied (M = 256: 7.5 MB through the pinned arena, 1 ms of host time)
-    const bool lean = eigfree && ss_active;
+    const bool lean = estep_route.eigfree;      // (on the scan chains: resolve_estep_route)
     auto pack_static = [&]() {
         if (static_packed) return;
         for (int i = 0; i < M; ++i) {
@@ -436,7 +410,7 @@ void smcpp_im::host_prep_and_upload() {
             gsc[g] = s_.scale;
             // (the eigenvalue powers (d_r / scale)^span of the group: k_group_dpow, on the device)
             // the scan steps apply the operator itself: their normalisers carry no eigenvalue scale (hybrid rows do: d / scale)
-            gls[g] = (ss_active && !(plan.hybrid && sp > plan.hyb_th)) ? 0.0 : sp * ls;
+            gls[g] = (estep_route.ss_active && !(plan.hybrid && sp > plan.hyb_th)) ? 0.0 : sp * ls;
         }
     };
     // M >= 128: a team of threads per eigen key (nonsym_eig_team.hpp: bit-identical to the serial routine); the size follows
@@ -454,7 +428,7 @@ void smcpp_im::host_prep_and_upload() {
         if ((int)l3.size() < Ke) team = 1;
     }
     bool team_done = false;
-    if (eigfree) {
+    if (estep_route.eigfree) {
         // no eigensystem is needed anywhere in this E-step: only the key-independent arrays are packed
         pack_static();
         for (int g = 0; g < G; ++g) { gsc[g] = 1.0; gls[g] = 0.0; }
@@ -518,7 +492,7 @@ void smcpp_im::host_prep_and_upload() {
     auto tp1 = std::chrono::steady_clock::now();
     std::vector<float> qTf;
     std::vector<double> qTdT, qPinvT, qPT, qPrm, qPinvrm;
-    if (Mp > 64 && plan.dense == ChainPlan::STREAMED_OPERANDS && !ss_active) {          // (the scan chains stream no operand)
+    if (Mp > 64 && plan.dense == ChainPlan::STREAMED_OPERANDS && !estep_route.ss_active) {          // (the scan chains stream no operand)
         // quarter-interleaved streaming layouts  Q[t][i][kq] = Mt[(kq*KQ + t)*Mp + i]  (k_fwd_big / k_bwd_big)
         const int KQ = Mp / 4;
         qTf.assign(MM, 0.f); qTdT.assign(MM, 0.0);
@@ -575,11 +549,10 @@ void smcpp_im::host_prep_and_upload() {
     }
     if (off > need) throw std::runtime_error("internal: parameter arena overflow");
     auto tp2 = std::chrono::steady_clock::now();
-    arena_side = lean && dual_stream;
     // SMCPP_DEBUG_POISON=nan: the whole arena is NaN again in front of its copy, on the copy's stream - a consumer that waits for the
     // copy sees this E-step's parameters, one that races it NaN instead of the previous E-step's plausible ones
-    if (opt().poison_nan) HIPCHK(hipMemsetAsync(d_param, 0xff, param_cap, arena_side ? stream2 : s));
-    if (arena_side) {
+    if (opt().poison_nan) HIPCHK(hipMemsetAsync(d_param, 0xff, param_cap, estep_route.arena_side ? stream2 : s));
+    if (estep_route.arena_side) {
         // nothing the chains read lives in this arena: the copy runs beside them, the statistics wait for it
         HIPCHK(hipMemcpyAsync(d_param, hb, off, hipMemcpyHostToDevice, stream2));
         HIPCHK(hipEventRecord(ev[EV_ARENA], stream2));
@@ -587,7 +560,7 @@ void smcpp_im::host_prep_and_upload() {
     HIPCHK(hipMemcpyAsync(d_param, hb, off, hipMemcpyHostToDevice, s));
     // (d_r / scale)^span for every (span, eigen key) group: G x M calls of pow() - 2 ms of host time on data with a few
     // thousand distinct spans, microseconds here
-    if (G > 0 && !eigfree)
+    if (G > 0 && !estep_route.eigfree)
         hipLaunchKernelGGL(k_group_dpow, dim3(ceil_div((long long)G * Mp, 256)), dim3(256), 0, s, G, M, Mp, (const int *)d_g_span.p,
                            (const int *)d_g_eig.p, (const double *)d_dsc.p, d_dpow.p);
     {

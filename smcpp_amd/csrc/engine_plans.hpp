@@ -787,7 +787,7 @@ void smcpp_im::run_stats() {
 }
 
 void smcpp_im::finish_stats() {
-    if (!(ss_active && done_covers_stats)) HIPCHK(hipStreamSynchronize(stream));      // (else: run_chains_ss saw the queue drain)
+    if (!(estep_route.ss_active && done_covers_stats)) HIPCHK(hipStreamSynchronize(stream));      // (else: run_chains_ss saw the queue drain)
     done_covers_stats = false;
     std::memcpy(loglik.data(), h_ll, sizeof(double) * n_contigs);
     stats_enqueued = false;
@@ -832,7 +832,7 @@ StatsPlan smcpp_im::resolve_stats_plan() {
     // path, and a hop between two streams costs ~10 us (2 us between two kernels of one queue): THAT branch keeps the main stream,
     // directly behind the chains and in front of the finalisation, and the span-1 branch (which has slack) forks.  (M > 64: chip-filling
     // rank updates, the hops do not matter and the other order is 3 % faster.)
-    const bool crit_main = eigfree && p.split && n_e_rows < 1000000 && Mp <= 64;
+    const bool crit_main = estep_route.eigfree && p.split && n_e_rows < 1000000 && Mp <= 64;
     p.span_gt1 = p.split && !crit_main ? P::SECOND : P::MAIN;
     p.span1 = crit_main ? P::SECOND : P::MAIN;
     // M <= 64, from half a million span-1 rows on: ONE pass over the key-sorted span-1 rows gives the rank update and the key's gamma
@@ -857,20 +857,20 @@ StatsPlan smcpp_im::resolve_stats_plan() {
     p.rank = Mp > 128 && !opt().off(smcpp_opt::O_RANK_WIDE) ? P::RANK_WIDE : teams ? P::RANK_TEAMS : P::RANK_PER_SLAB;
     p.teams_span1 = teams && !teams_rk.empty();
     p.teams_one_pass = teams && !teams_fk.empty();
-    p.teams_span_gt1 = teams && eigfree && !teams_eg.empty();
-    if (eigfree) p.eigen = slabs_eg.empty() ? P::EIG_NONE : ss_active && !opt().off(smcpp_opt::O_SPAN_SCAN) ? P::EIG_FOLD_SCANS : P::EIG_FOLD_MATRIX_CORES;
+    p.teams_span_gt1 = teams && estep_route.eigfree && !teams_eg.empty();
+    if (estep_route.eigfree) p.eigen = slabs_eg.empty() ? P::EIG_NONE : estep_route.ss_active && !opt().off(smcpp_opt::O_SPAN_SCAN) ? P::EIG_FOLD_SCANS : P::EIG_FOLD_MATRIX_CORES;
     else p.eigen = NT <= 4 && !slabs_eg.empty() ? P::EIG_GEN2 : P::EIG_CLASSIC;
     // the span fold (tens of serial steps on a few CUs) ends the longest dependency chain, so what it waits for goes FIRST and alone
     // (small inputs only: from ~10^6 span > 1 rows on, the two rank updates side by side finish sooner - whole genome 3.76 -> 3.36 ms)
-    p.rank_early = eigfree && p.split && n_e_rows < 1000000;
+    p.rank_early = estep_route.eigfree && p.split && n_e_rows < 1000000;
     if (save_gamma && n_e_rows > 0) {
         // long rows at 64 < M <= 256 with a structured T: eigen-power pieces + scan steps, which read the statistics' U / W products
         // (main stream, behind them); the other forms need alpha, beta and the eigensystems only: beside the statistics
-        const bool pieces = !eigfree && NT > 4 && Mp <= 256 && !opt().off(smcpp_opt::O_GAMMA_PIECES) &&
-                            (double)gamma_piece_count() * Mp * 20.0 < 96e9 && (ss_active || ss_generators_only());
+        const bool pieces = !estep_route.eigfree && NT > 4 && Mp <= 256 && !opt().off(smcpp_opt::O_GAMMA_PIECES) &&
+                            (double)gamma_piece_count() * Mp * 20.0 < 96e9 && (estep_route.ss_active || ss_generators_only());
         p.gamma_beside = dual && !pieces && !opt().off(smcpp_opt::O_GAMMA_SIDE);
         p.gamma = p.gamma_beside ? P::HIGH : P::MAIN;
-        p.gamma_form = pieces ? P::GAMMA_PIECES : eigfree ? P::GAMMA_SCAN : NT <= 4 ? P::GAMMA_EIG_BATCHES : P::GAMMA_EIG_ROWS;
+        p.gamma_form = pieces ? P::GAMMA_PIECES : estep_route.eigfree ? P::GAMMA_SCAN : NT <= 4 ? P::GAMMA_EIG_BATCHES : P::GAMMA_EIG_ROWS;
     }
     // the finalisation signals the host itself when nothing follows it on the main stream and the launch is small: every block ends
     // with a device-scope fence and an atomic on ONE counter (1 500 contigs: 3.2 ms; beyond 128 blocks the one-thread kernel signals)
@@ -882,8 +882,8 @@ StatsPlan smcpp_im::resolve_stats_plan() {
 // and the emission table (a wait in front of the fork event instead costs 12 us per eval: every branch then starts behind the barrier
 // packet; on the side streams, which have slack, it costs nothing measurable)
 void smcpp_im::fork_from_chains(hipStream_t x) {
-    HIPCHK(hipStreamWaitEvent(x, ev[ss_active ? EV_CHAINS_END : EV_STATS_FORK], 0));
-    if (arena_side) HIPCHK(hipStreamWaitEvent(x, ev[EV_ARENA], 0));
+    HIPCHK(hipStreamWaitEvent(x, ev[estep_route.ss_active ? EV_CHAINS_END : EV_STATS_FORK], 0));
+    if (estep_route.arena_side) HIPCHK(hipStreamWaitEvent(x, ev[EV_ARENA], 0));
 }
 
 // weights (and, span-1 rows, partial gamma sums and save_gamma's rows) of the span-1 rows, or only the weights of the span > 1 rows
@@ -1140,8 +1140,8 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
         HIPCHK(hipHostGetDevicePointer((void **)&d_ll_view, h_ll, 0));
     }
     // the parameter arena of a lean E-step (Td, the emission table of a set_raw manager, the groups' log-scales) is copied on the
-    // second stream beside the chains (engine_params.hpp: arena_side); every stream of the statistics waits for it
-    if (arena_side) HIPCHK(hipStreamWaitEvent(s, ev[EV_ARENA], 0));
+    // second stream beside the chains (EstepRoute::arena_side); every stream of the statistics waits for it
+    if (estep_route.arena_side) HIPCHK(hipStreamWaitEvent(s, ev[EV_ARENA], 0));
     if (save_gamma) {
         d_gamma_rows.alloc((size_t)total_rows * Mp);
         // Every row 1 .. L of a contig is written whole by the statistics (span-1 rows: k_s1_scalars; span > 1 rows: the per-row gamma
@@ -1153,7 +1153,7 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
     }
     // ---- fork ----
     if (p.split) {
-        if (!ss_active) HIPCHK(hipEventRecord(ev[EV_STATS_FORK], s));
+        if (!estep_route.ss_active) HIPCHK(hipEventRecord(ev[EV_STATS_FORK], s));
         fork_from_chains(stream2);
     }
     // ---- log-likelihood (also materialises log_c per row) ----
@@ -1176,11 +1176,11 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
     fa.Z = d_Z.p; fa.Y = d_Y.p; fa.xisum = d_xisum.p; fa.gsum = d_gsum.p; fa.gamma0 = d_gamma0.p;
     fa.dpow = d_dpow.p;
     fa.part_e = nullptr;
-    fa.eigfree = eigfree ? 1 : 0;
+    fa.eigfree = estep_route.eigfree ? 1 : 0;
     if (!slabs_eg.empty() && p.eigen != StatsPlan::EIG_GEN2) {
         d_part_e.alloc(std::max<size_t>(1, p.teams_span_gt1 ? teams_eg.size() : slabs_eg.size()) * Mp * Mp);
         fa.part_e = d_part_e.p;
-        if (eigfree) { d_red_e.alloc(std::max<size_t>(1, eb_gid.size()) * Mp * Mp); fa.red_e = d_red_e.p; }
+        if (estep_route.eigfree) { d_red_e.alloc(std::max<size_t>(1, eb_gid.size()) * Mp * Mp); fa.red_e = d_red_e.p; }
     }
     // ---- the two branches ----
     if (p.rank_early) {
@@ -1268,7 +1268,7 @@ void smcpp_im::resolve_timing() {
     HIPCHK(hipSetDevice(device));
     (void)hipEventSynchronize(ev[EV_STATS_DONE]);
     float f_ms = 0, b_ms = 0, s_ms = 0, fin_ms = 0;
-    if (ss_active) {
+    if (estep_route.ss_active) {
         // one launch per pass for both directions, timed below
     } else if (chains_dual) {
         (void)hipEventElapsedTime(&f_ms, ev[EV_CHAINS_START], ev[EV_FWD_END]);   // forward passes (main stream)
@@ -1278,7 +1278,7 @@ void smcpp_im::resolve_timing() {
         (void)hipEventElapsedTime(&b_ms, ev[EV_BWD_START], ev[EV_CHAINS_END]);
     }
     float chains_ms = 0;
-    if (ss_active) {
+    if (estep_route.ss_active) {
         // every pass of both directions between two events: EV_FIRST_PASS in front of the first launch, EV_CHAINS_END behind the last
         // one (a rare round that needs more passes than were launched up front includes the host's look at the flags)
         (void)hipEventElapsedTime(&chains_ms, ev[EV_FIRST_PASS], ev[EV_CHAINS_END]);
@@ -1299,6 +1299,24 @@ void smcpp_im::resolve_timing() {
     timing[2] = f_ms; timing[3] = b_ms; timing[4] = s_ms; timing[5] = fin_ms;
     timing[6] = t_host12;
     timing[7] = last_fwd_passes; timing[8] = last_bwd_passes;
+}
+
+// structured_T: what ss_extract_generators() found; in front of it plan.scan, "not disproved yet" - then only the first refusal can fire.
+EstepRoute smcpp_im::resolve_estep_route(bool structured_T) const {
+    EstepRoute r;
+    // span > 1 rows without an eigensystem (k_span_fold); with save_gamma their per-row posteriors come from scan steps too (k_gamma_rows_scan)
+    r.eigfree_static = !opt().off(smcpp_opt::O_EIGFREE) && Mp <= 1024 && ss_max_span <= 64 && (!save_gamma || !opt().off(smcpp_opt::O_GAMMA_SCAN));
+    r.ss_active = structured_T;
+    r.eigfree = r.ss_active && r.eigfree_static;
+    if (Mp > 256 && !(plan.scan && r.eigfree_static))
+        r.refuse = "more than 256 hidden states: only the scan chains with eigen-free statistics are built (rows longer than 64 positions are cut "
+                   "into pieces at construction unless SMCPP_SPLIT_SPANS=0 / SMCPP_EIGFREE=0 forbid it or the pieces would not fit the device)";
+    else if (Mp > 256 && !r.ss_active)
+        r.refuse = "more than 256 hidden states: the transition matrix must have the structure of the reference's "
+                   "HJTransition (the dense fallback kernels stop at 256)";
+    r.host_E = E_on_dev && !r.eigfree;       // only the lean path reads a device-prepared table from HBM alone (its kernel checks the underflow bound)
+    r.arena_side = r.eigfree && dual_stream; // lean E-steps copy the (small) parameter arena on stream2 beside the chains (EV_ARENA)
+    return r;
 }
 
 void smcpp_im::estep() {
@@ -1322,43 +1340,27 @@ void smcpp_im::estep() {
         HIPCHK(hipMemsetAsync(d_gamma_rows.p, 0xff, sizeof(double) * d_gamma_rows.n, stream));
     }
     HIPCHK(hipEventRecord(ev[EV_ESTEP], stream));
-    // span > 1 rows without an eigensystem (kernels.hpp: k_span_fold): the span is expanded by smax steps of two M x M products
-    const bool eigfree_off = opt().off(smcpp_opt::O_EIGFREE);
-    // (round 6) save_gamma keeps the eigen-free path: the per-row posteriors of the span > 1 rows come from scan steps as well
-    // (chains_ss.hpp: k_gamma_rows_scan); SMCPP_GAMMA_SCAN=0: eigensystems, as in rounds 1-5 (M <= 256)
-    const bool gamma_scan = !opt().off(smcpp_opt::O_GAMMA_SCAN);
-    const bool eigfree_static = !eigfree_off && Mp <= 1024 && ss_max_span <= 64 && (!save_gamma || gamma_scan);
-    if (Mp > 256 && !(plan.scan && eigfree_static))
-        throw std::runtime_error("more than 256 hidden states: only the scan chains with eigen-free statistics are built (rows longer than "
-                                 "64 positions are cut into pieces at construction unless SMCPP_SPLIT_SPANS=0 / SMCPP_EIGFREE=0 forbid it or "
-                                 "the pieces would not fit the device)");
-    // only the lean path (scan chains + eigen-free statistics) reads a device-prepared emission table from HBM alone (its
-    // underflow bound is checked by the kernel that forms the table); eigensystems, operand layouts, the dense chains and the
-    // bound for longer spans need the host copy
-    if (E_on_dev && !(plan.scan && eigfree_static)) sync_host_E();
-    ss_active = plan.scan && ss_extract_generators();
-    if (Mp > 256 && !ss_active)
-        throw std::runtime_error("more than 256 hidden states: the transition matrix must have the structure of the reference's "
-                                 "HJTransition (the dense fallback kernels stop at 256)");
+    EstepRoute er = resolve_estep_route(plan.scan);                  // in front of the generators: T may have the structure
+    if (er.refuse) throw std::runtime_error(er.refuse); if (er.host_E) sync_host_E();
+    er = resolve_estep_route(plan.scan && ss_extract_generators());  // ... and with what they say about T
+    if (er.refuse) throw std::runtime_error(er.refuse); if (er.host_E) sync_host_E();       // (refused: estep_route stays the last E-step's)
+    estep_route = er;
     tr.mark("estep: extract generators");
-    if (!ss_active) ss_warm_valid = false;
-    eigfree = ss_active && eigfree_static;
-    if (E_on_dev && !(ss_active && eigfree)) sync_host_E();      // (a transition matrix without the structure)
-    if (ss_active && !plan.hybrid) { prepass_launched = false; static_packed = false; ss_launch_initial(); }   // the chains need no eigensystem: they start now
-    else if (ss_active) { prepass_launched = false; static_packed = false; }
-    else stage_static_and_prepass();   // (when eligible) pass 0 of both chains starts now, on eigen-free operands
+    prepass_launched = false;
+    if (!estep_route.ss_active) { ss_warm_valid = false; stage_static_and_prepass(); }   // (when eligible) pass 0 of both chains starts now, on eigen-free operands
+    else { static_packed = false; if (!plan.hybrid) ss_launch_initial(); }               // the chains need no eigensystem: they start now
     tr.mark("estep: first launches");
     host_prep_and_upload();   // the reference rebuilds the eigensystems on every E-step (inference_manager.cpp:112)
     tr.mark("estep: host_prep_and_upload");
-    if (ss_active && plan.hybrid) ss_launch_initial();       // hybrid rows read the eigensystems: the chains start behind them
+    if (estep_route.ss_active && plan.hybrid) ss_launch_initial();       // hybrid rows read the eigensystems: the chains start behind them
     auto t1 = std::chrono::steady_clock::now();
-    if (ss_active) run_chains_ss(); else run_chains();
+    if (estep_route.ss_active) run_chains_ss(); else run_chains();
     tr.mark("estep: chains (host view)");
     run_stats();
     tr.mark("estep: statistics enqueued");
     if (E_on_dev) {
         dprep->check_flags();
-        if (ss_active && dprep->flags()[2]) {
+        if (estep_route.ss_active && dprep->flags()[2]) {
             // an emission entry so small that `span` scan steps underflow (ss_extract_generators' bound, evaluated by the kernel
             // that formed the table): this E-step is redone on the dense kernels from the host copy of the same parameters
             sync_host_E();

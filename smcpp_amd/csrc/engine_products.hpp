@@ -257,7 +257,7 @@ void smcpp_im::post_transitions_check() {
                                  "belong to the earlier ones: run the E-step again");
     // the scan chains of the last E-step ran on these generators; an E-step on the dense kernels (long un-cut rows beyond 64
     // states, SMCPP_SS=0, SMCPP_CHAIN, SMCPP_HYBRID=0) stored the same vectors: its T is looked at here
-    if (!ss_active && !ss_generators_only())
+    if (!estep_route.ss_active && !ss_generators_only())
         throw std::runtime_error("posterior transitions: the transition matrix does not have the semiseparable structure of the "
                                  "model's (smcpp_set_raw with an arbitrary matrix): the O(M) steps that walk a row's interior do "
                                  "not exist for it");
@@ -987,20 +987,7 @@ void smcpp_im::score_tables() {
     std::vector<double> Eloc, dEloc;
     const std::vector<double> *Ev = &E, *dEv = &dE;
     if (E_on_dev) {
-        HIPCHK(hipStreamSynchronize(stream));
-        std::vector<double> Ep, dEp, em, dem;
-        dprep->fetch(Ep, dEp, em, dem, false);           // (the table and its Jacobian alone)
-        dprep->check_flags();
-        if (!have_global) { Eloc.swap(Ep); dEloc.swap(dEp); }
-        else {
-            Eloc.assign((size_t)K * M, 0.0);
-            dEloc.assign((size_t)K * M * nder, 0.0);
-            for (int k = 0; k < K; ++k) {
-                const int kg = local_to_global[k];
-                std::memcpy(&Eloc[(size_t)k * M], &Ep[(size_t)kg * M], sizeof(double) * M);
-                std::memcpy(&dEloc[(size_t)k * M * nder], &dEp[(size_t)kg * M * nder], sizeof(double) * M * nder);
-            }
-        }
+        fetch_prepared_table(Eloc, dEloc, false);          // (the table and its Jacobian alone; nder >= 1 here: score_check)
         Ev = &Eloc; dEv = &dEloc;
     }
     const size_t nd = (size_t)nder;
