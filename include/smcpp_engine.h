@@ -180,7 +180,8 @@ int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *row
  * sizes and distinguished lineages of the npop populations, as smcpp_create_onepop / _twopop take them) would resolve on a device
  * of `compute_units` compute units after smcpp_set_chunking(rows_per_chunk) (0: automatic), and the chunk lists it would cut.
  * Runs the host half of the construction - keys, rows, groups, the cut of long rows - and the same resolve and cut functions a
- * manager runs.  json (up to json_cap - 1 characters): {"plan": {..., "power_jumps": {...}}} as smcpp_describe prints it, with the
+ * manager runs.  json (up to json_cap - 1 characters): {"plan": {..., "power_jumps": {...}}, "hybrid": {...} | null}
+ * (the form of the hybrid rows' eigen-power step: tables in LDS, cold and hot eigen keys) as smcpp_describe prints it, with the
  * per-E-step entries ("light_passes_*", "halo_pass", "float_scans_in_stored_passes", "passes_launched", "power_jumps.run") as a first
  * E-step on a transition matrix of the reference's structure sets them.  chunks_fwd / chunks_bwd: up to chunk_cap chunks each in
  * smcpp_debug_chunks' five-int format.  lengths[3]: what the text and the two lists need (call with the caps 0 to size them). */

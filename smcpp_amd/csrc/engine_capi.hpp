@@ -513,8 +513,27 @@ int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out) {
 // Every SMCPP_* switch is parsed once per process (engine_options.hpp); this re-reads the environment.
 void smcpp_reload_options(void) { smcpp_opt::reload(); }
 
+// The "hybrid" object of smcpp_describe, beside "plan": which form of the hybrid rows' eigen-power step the manager's ChainPlan holds
+// (null: no hybrid rows) - the values run_chains_ss hands to SsArgs, nothing recomputed.  Eigen keys by their index (the order of the
+// key list among the keys of span > 1 rows); cold: no LDS slot, table rows from L2; hot: the key whose rows stay in registers (Mp = 32).
+static std::string describe_hybrid(const smcpp_im *im) {
+    static const char *const form[] = {"", "all tables", "direction split", "direction split, cold keys"};
+    const ChainPlan &p = im->plan;
+    if (!p.hybrid) return ", \"hybrid\": null";
+    std::string cold;
+    for (int e = 0; e < im->Ke; ++e)
+        if (p.eslot_of_key[e] < 0) cold += (cold.empty() ? "" : ", ") + std::to_string(e);
+    char t[512];
+    snprintf(t, sizeof t, ", \"hybrid\": {\"form\": \"%s\", \"threshold\": %d, \"eigen_keys\": %d, \"tables_in_lds\": %d, \"cold_eigen_keys\": [%s], "
+             "\"hot_eigen_key\": %d, \"workgroup_wavefronts\": %d, \"emission_slots_in_lds\": %d, \"all_keys_in_lds\": %s}",
+             form[p.hybrid], p.hyb_th, im->Ke, p.nk_lds, cold.c_str(), im->Mp == 32 ? std::max(0, im->hot_eig) : -1, p.wg_waves, p.nlds,
+             p.all_keys_in_lds ? "true" : "false");
+    return t;
+}
+
 // The "plan" object of smcpp_describe (with "power_jumps" inside): every value read from the manager's ChainPlan, the ChainPass of its
-// last E-step on the scan chains, or what the E-steps learned.  smcpp_host_chain_plan prints a host-only manager through it.
+// last E-step on the scan chains, or what the E-steps learned; the "hybrid" object follows it.  smcpp_host_chain_plan prints a
+// host-only manager through it.
 static std::string describe_chain_plan(const smcpp_im *im) {
     char t[1024];
     const ChainPlan &p = im->plan;
@@ -542,7 +561,7 @@ static std::string describe_chain_plan(const smcpp_im *im) {
     snprintf(t, sizeof t, ", \"power_jumps\": {\"eligible\": %s, \"run\": %s, \"key\": %d, \"key_slot\": %d, \"powers\": [%s]}}",
              el ? "true" : "false", cp.jump ? "true" : "false", el ? p.jump_kid : -1,
              el && !im->ss_slot_of_key.empty() ? im->ss_slot_of_key[p.jump_kid] : -1, el ? std::to_string(p.jump_P).c_str() : "");
-    return s + t;
+    return s + t + describe_hybrid(im);
 }
 
 // "parameters" of smcpp_describe: the plan of the last prepare_params() / set_raw, where the tables live NOW, the last E-step's route

@@ -700,6 +700,17 @@ void smcpp_im::build_layout(int npop_, const int *nn, const int *nna, int n_cont
     ss_max_span = 1;
     for (const Group &g : groups) ss_max_span = std::max(ss_max_span, g.span);
     {
+        // the "hot" eigen key (most span > 1 rows; the second one: most of the rest) the chain kernels keep in registers
+        std::vector<long long> cnt(std::max(1, Ke), 0);
+        for (const RowInfo &ri : rowinfo)
+            if (ri.gid >= 0) cnt[groups[ri.gid].eig]++;
+        hot_eig = hot_eig2 = -1;
+        for (int e = 0; e < Ke; ++e)
+            if (hot_eig < 0 || cnt[e] > cnt[hot_eig]) hot_eig = e;
+        for (int e = 0; e < Ke; ++e)
+            if (e != hot_eig && (hot_eig2 < 0 || cnt[e] > cnt[hot_eig2])) hot_eig2 = e;
+    }
+    {
         // key slots of the scan chains: slot = frequency rank of the key (slot 0 = most rows; the emission vectors of the first
         // ChainPlan::nlds slots live in LDS)
         std::vector<long long> kc(K, 0);
@@ -1326,22 +1337,15 @@ void smcpp_im::alloc_device() {
     hipStream_t s = stream;
     d_rowinfo.upload(rowinfo, s);
     {
-        // packed descriptors of the chain kernels and the "hot" eigen key (most span>1 rows) they keep in registers
+        // packed descriptors of the chain kernels
         // ROWDESC_PAD span-1 descriptors of key 0 on both sides: the chain kernels prefetch descriptors up to 192 rows
         // past either end of a chunk without bounds tests (chains2.hpp)
         std::vector<int2> rd((size_t)total_rows + 2 * ROWDESC_PAD, make_int2(0, -1));
-        std::vector<long long> cnt(std::max(1, Ke), 0);
         for (size_t r = 0; r < (size_t)total_rows; ++r) {
             const RowInfo &ri = rowinfo[r];
             rd[ROWDESC_PAD + r].x = ri.kid;
             rd[ROWDESC_PAD + r].y = ri.gid < 0 ? -1 : (ri.gid | (groups[ri.gid].eig << 20));
-            if (ri.gid >= 0) cnt[groups[ri.gid].eig]++;
         }
-        hot_eig = hot_eig2 = -1;
-        for (int e = 0; e < Ke; ++e)
-            if (hot_eig < 0 || cnt[e] > cnt[hot_eig]) hot_eig = e;
-        for (int e = 0; e < Ke; ++e)
-            if (e != hot_eig && (hot_eig2 < 0 || cnt[e] > cnt[hot_eig2])) hot_eig2 = e;
         d_rowdesc.upload(rd, s);
         HIPCHK(hipStreamSynchronize(s));
     }
