@@ -194,6 +194,17 @@ int smcpp_host_chain_plan(int npop, const int *n, const int *na, int n_contigs, 
  * Writes at most json_cap - 1 characters; *length: what the text needs (call with json_cap 0 to size the buffer). */
 int smcpp_host_param_plan(int npop, int have_raw, int force_host, int nder, int n, int pieces_plus_states, int have_global,
                           char *json, int json_cap, int *length);
+/* Host-only (no device needed, none touched): the plan of the statistics phase and the layout it runs on, for a manager built from
+ * the observation arguments of smcpp_host_chain_plan on a device of `compute_units` compute units, with save_gamma on or off.
+ * structured_T != 0: the transition matrix has the reference's structure - the E-step runs on the scan chains where the chain plan
+ * takes them, and generators of T exist.  json: {"statistics": {...}, "layout": {...}}: "statistics" as smcpp_describe prints it after
+ * such an E-step; "layout": what the construction cut for the statistics kernels - rows of span 1 and span > 1, rows per slab, whether
+ * the slab count was aimed at teams, the shares of the reductions, the blocks of the log-likelihood reduction, the eigen-power pieces
+ * and, per list, its length and the 64-bit FNV-1a hash of its elements (little-endian, field by field); a slab list adds the rows its
+ * slabs hold, its padding slabs and whether the slabs tile the sorted rows in order.  Writes at most json_cap - 1 characters;
+ * *length: what the text needs (call with json_cap 0 to size the buffer). */
+int smcpp_host_stats_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs, int n_hs,
+                          const double *hs, int compute_units, int save_gamma, int structured_T, char *json, int json_cap, int *length);
 int smcpp_chain_mode(smcpp_im *im);
 /* diagnostics (host only): the chunk list of the scan chains as the last plan cut it - backward == 0: the forward chain's, else the
  * backward chain's (the two directions have lists of their own).  Writes up to `cap` chunks into out[5 * cap] as (contig, r0, r1, h0,

@@ -97,6 +97,24 @@ def host_chain_plan(n, na, contigs, hs, compute_units, rows_per_chunk=0):
     return json.loads(buf.value.decode()), fwd[:need[1]], bwd[:need[2]]
 
 
+def host_stats_plan(n, na, contigs, hs, compute_units, save_gamma=False, structured_T=True):
+    """The statistics plan and layout a manager of these contigs would resolve on a device of `compute_units` compute units, without
+    a device (`smcpp_host_stats_plan`): -> {"statistics": describe()'s object, "layout": counts and per-list length + FNV-1a hash}."""
+    import json
+    n = np.ascontiguousarray(np.atleast_1d(n), dtype=np.int32)
+    na = np.ascontiguousarray(np.atleast_1d(na), dtype=np.int32)
+    obs = [np.ascontiguousarray(c, dtype=np.int32) for c in contigs]
+    Ls = np.array([c.shape[0] for c in obs], dtype=np.int32)
+    ptrs = (_ip * len(obs))(*[iptr(c) for c in obs])
+    hs = np.ascontiguousarray(hs, dtype=np.float64)
+    head = (len(n), iptr(n), iptr(na), len(obs), iptr(Ls), ptrs, len(hs), dptr(hs), int(compute_units), int(bool(save_gamma)), int(bool(structured_T)))
+    need = C.c_int(0)
+    check(lib().smcpp_host_stats_plan(*head, None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value + 1)
+    check(lib().smcpp_host_stats_plan(*head, buf, need.value + 1, C.byref(need)))
+    return json.loads(buf.value.decode())
+
+
 def host_param_plan(npop=1, have_raw=False, force_host=False, nder=0, n=4, pieces_plus_states=33, have_global=False):
     """The "parameters" object of describe() for a manager in this state under the switches of the environment, without a device
     (`smcpp_host_param_plan`); the entries an E-step or a getter changes are as a fresh manager has them."""

@@ -80,6 +80,7 @@ cdef extern from "smcpp_engine.h":
     int smcpp_host_chunk_counts(int n_contigs, const long long *cost, const int *rows, long long nslots, long long floor_cost, int *out) nogil
     int smcpp_host_chain_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs, int n_hs, const double *hs, int compute_units, int rows_per_chunk, char *json, int json_cap, int *chunks_fwd, int *chunks_bwd, int chunk_cap, int *lengths) nogil
     int smcpp_host_param_plan(int npop, int have_raw, int force_host, int nder, int n, int pieces_plus_states, int have_global, char *json, int json_cap, int *length) nogil
+    int smcpp_host_stats_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs, int n_hs, const double *hs, int compute_units, int save_gamma, int structured_T, char *json, int json_cap, int *length) nogil
     int smcpp_chain_mode(smcpp_im *im) nogil
     int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out) nogil
     void smcpp_reload_options() nogil

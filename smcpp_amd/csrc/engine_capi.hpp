@@ -577,6 +577,26 @@ static std::string describe_param_plan(const smcpp_im *im) {
     return p.source != ParamPlan::NONE ? t : ", \"parameters\": null";
 }
 
+// "statistics" of smcpp_describe: the statistics plan of the last E-step (null before the first one) - the stream of every branch, the
+// form of every kernel family.  smcpp_host_stats_plan prints a host-only manager through it.
+static std::string describe_stats_plan(const smcpp_im *im) {
+    char t[1024];
+    const StatsPlan &p = im->stats_plan;
+    static const char *const stream[] = {"main", "second", "third", "high priority"}, *const rank[] = {"per slab", "teams", "wide"};
+    static const char *const eigen[] = {"none", "fold on the scans", "fold on the matrix cores", "generation 2", "classic"};
+    static const char *const gsum[] = {"one pass", "own stream", "span > 1 tail", "span-1 branch"};
+    static const char *const gamma[] = {"none", "scan steps", "eigen-power pieces + scan steps", "eigensystem batches", "eigensystem rows"};
+    snprintf(t, sizeof t,
+             ", \"statistics\": {\"span_gt1_stream\": \"%s\", \"span1_stream\": \"%s\", \"gamma_sums_stream\": \"%s\", "
+             "\"loglik_stream\": \"%s\", \"per_row_gamma_stream\": \"%s\", \"span1_form\": \"%s\", \"rank_update\": \"%s\", "
+             "\"eigen\": \"%s\", \"span_gt1_rank_early\": %s, \"gamma_sums_reduced\": \"%s\", \"per_row_gamma\": \"%s\", "
+             "\"per_row_gamma_beside\": %s, \"slab_rows_span1\": %d, \"slab_rows_span_gt1\": %d, \"reduction_shares\": %d}",
+             stream[p.span_gt1], stream[p.span1], stream[p.gsum], stream[p.loglik], stream[p.gamma], p.s1_one_pass ? "one pass" : "two kernels",
+             rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false",
+             im->lay.slab_rows_1, im->lay.slab_rows_e, im->lay.ZS);
+    return p.resolved ? t : ", \"statistics\": null";
+}
+
 // One JSON object: the switches found in the environment and the plan this manager resolved from them and from its input (chain
 // family, states per lane, chunk counts, history passes, arithmetic of the stored passes and the statistics plan of the LAST
 // E-step).  Returns the length the text needs (without the terminating zero); writes at most cap - 1 characters.
@@ -586,21 +606,7 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
     if (im) {
         char t[1024];
         s += describe_chain_plan(im);
-        // the statistics plan of the last E-step (null before the first one): the stream of every branch, the form of every kernel family
-        const StatsPlan &p = im->stats_plan;
-        static const char *const stream[] = {"main", "second", "third", "high priority"}, *const rank[] = {"per slab", "teams", "wide"};
-        static const char *const eigen[] = {"none", "fold on the scans", "fold on the matrix cores", "generation 2", "classic"};
-        static const char *const gsum[] = {"one pass", "own stream", "span > 1 tail", "span-1 branch"};
-        static const char *const gamma[] = {"none", "scan steps", "eigen-power pieces + scan steps", "eigensystem batches", "eigensystem rows"};
-        snprintf(t, sizeof t,
-                 ", \"statistics\": {\"span_gt1_stream\": \"%s\", \"span1_stream\": \"%s\", \"gamma_sums_stream\": \"%s\", "
-                 "\"loglik_stream\": \"%s\", \"per_row_gamma_stream\": \"%s\", \"span1_form\": \"%s\", \"rank_update\": \"%s\", "
-                 "\"eigen\": \"%s\", \"span_gt1_rank_early\": %s, \"gamma_sums_reduced\": \"%s\", \"per_row_gamma\": \"%s\", "
-                 "\"per_row_gamma_beside\": %s, \"slab_rows_span1\": %d, \"slab_rows_span_gt1\": %d, \"reduction_shares\": %d}",
-                 stream[p.span_gt1], stream[p.span1], stream[p.gsum], stream[p.loglik], stream[p.gamma], p.s1_one_pass ? "one pass" : "two kernels",
-                 rank[p.rank], eigen[p.eigen], p.rank_early ? "true" : "false", gsum[p.gsum_at], gamma[p.gamma_form], p.gamma_beside ? "true" : "false",
-                 im->slab_rows_1, im->slab_rows_e, im->ZS);
-        s += p.resolved ? t : ", \"statistics\": null";
+        s += describe_stats_plan(im);
         // who evaluated the last smcpp_q: the device kernels (q_device), the host loops, or nobody yet
         static const char *const route[] = {"none", "device", "host"};
         s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";

@@ -399,3 +399,72 @@ int smcpp_host_param_plan(int npop, int have_raw, int force_host, int nder, int 
 }
 
 }  // extern "C"
+
+// ---- the layout of the statistics, printed: per list its length and a 64-bit FNV-1a hash of its elements, field by field ----
+namespace {
+struct Fnv {
+    unsigned long long h = 0xcbf29ce484222325ull;
+    void word(unsigned long long v, int bytes) { for (int b = 0; b < bytes; ++b) { h ^= (v >> (8 * b)) & 0xff; h *= 0x100000001b3ull; } }
+    void add(int v) { word((unsigned)v, 4); }
+    void add(const int2 &v) { add(v.x); add(v.y); }
+    void add(const int4 &v) { add(v.x); add(v.y); add(v.z); add(v.w); }
+    void add(const Slab &v) { add(v.start); add(v.end); add(v.bucket); add(v.aux); word((unsigned long long)v.base, 8); }
+};
+template <class T>
+std::string list_json(const char *name, const std::vector<T> &v) {
+    Fnv f;
+    for (const T &x : v) f.add(x);
+    char t[160];
+    snprintf(t, sizeof t, "\"%s\": {\"n\": %zu, \"fnv1a\": \"%016llx\"", name, v.size(), f.h);
+    return t;
+}
+// a slab list also says how many rows its slabs hold, how many of them are padding (empty) and whether they tile the sorted rows
+// 0 .. rows in order, each slab beginning where the one before it ends: every row in exactly one slab
+std::string slabs_json(const char *name, const std::vector<Slab> &v) {
+    long long rows = 0, pad = 0, at = 0;
+    bool tiles = true;
+    for (const Slab &s : v) { rows += s.end - s.start; pad += s.end == s.start; tiles = tiles && s.start == at && s.end >= s.start; at = s.end; }
+    char t[160];
+    snprintf(t, sizeof t, ", \"rows\": %lld, \"padding\": %lld, \"tiles_the_rows\": %s}", rows, pad, tiles ? "true" : "false");
+    return list_json(name, v) + t;
+}
+}  // namespace
+
+extern "C" {
+
+// The statistics plan and layout of a manager that exists on the host only: build_layout, make_chunks, the layout cut, the route and
+// the plan of a first E-step.  structured_T: the E-step runs on the scan chains (if the chain plan takes them) and T has generators.
+int smcpp_host_stats_plan(int npop, const int *n, const int *na, int n_contigs, const int *Ls, const int *const *obs, int n_hs,
+                          const double *hs, int compute_units, int save_gamma, int structured_T, char *json, int json_cap, int *length) {
+    API_BEGIN
+    if (npop < 1 || npop > 2 || compute_units <= 0) throw std::runtime_error("smcpp_host_stats_plan: one or two populations, at least one compute unit");
+    smcpp_im im;
+    im.build_layout(npop, n, na, n_contigs, Ls, obs, n_hs, hs, 0.5);
+    im.cu_count = compute_units;
+    im.make_chunks();
+    im.lay = im.cut_stats_layout();
+    im.save_gamma = save_gamma != 0;
+    im.read_dual_stream();
+    im.estep_route = im.resolve_estep_route(im.plan.scan && structured_T != 0);
+    im.stats_plan = im.resolve_stats_plan(im.gamma_pieces_fit() && structured_T != 0);
+    const StatsLayout &l = im.lay;
+    char t[512];
+    snprintf(t, sizeof t, "{\"rows_span1\": %lld, \"rows_span_gt1\": %lld, \"slab_rows_span1\": %d, \"slab_rows_span_gt1\": %d, \"teams\": %s, "
+             "\"reduction_shares\": %d, \"gamma_sum_shares\": %d, \"loglik_blocks\": %d, \"pieces\": %lld, \"lists\": {",
+             l.n_1_rows, l.n_e_rows, l.slab_rows_1, l.slab_rows_e, l.teams ? "true" : "false", l.ZS, l.ZG, l.llblk, l.pieces);
+    std::string lay = t;
+#define L_(x) lay += list_json(#x, l.x.h) + "}, ";
+    L_(perm1) L_(perm1k) L_(perme) L_(gk_slab_off) L_(s1_slab_off) L_(eb_slab_off) L_(eb_gid) L_(ce_bucket_off) L_(erow_slab)
+    L_(fk_c_off) L_(fk_gk_off) L_(ek_slab_off) L_(epos_gid) L_(erow_desc) L_(teams_fk) L_(teams_eg) L_(teams_rk) L_(fk_c_team_off)
+    L_(eb_team_off) L_(s1_team_off)
+#undef L_
+    lay += list_json("ce_row_off", l.ce_row_off) + "}, ";
+    lay += slabs_json("slabs_sc", l.slabs_sc.h) + ", " + slabs_json("slabs_rk", l.slabs_rk.h) + ", " + slabs_json("slabs_eg", l.slabs_eg.h) + ", " +
+           slabs_json("slabs_fk", l.slabs_fk.h) + ", " + slabs_json("slabs_ek", l.slabs_ek.h) + "}}";
+    const std::string s = "{" + describe_stats_plan(&im).substr(2) + ", \"layout\": " + lay + "}";
+    if (json && json_cap > 0) snprintf(json, (size_t)json_cap, "%s", s.c_str());
+    if (length) *length = (int)s.size();
+    API_END
+}
+
+}  // extern "C"

@@ -20,6 +20,53 @@ struct StatsPlan {
     Gamma gamma_form = GAMMA_NONE;
     bool gamma_beside = false;             // the per-row gammas run beside the statistics
     bool fin_signals = false;              // the finalisation may raise the completion word itself
+    // counts a launch and an allocation both read (size_stats_buffers): partials of the span-1 rank update (per team or per slab of
+    // the form that runs) and of the span > 1 one (0: none), gamma partials of the one-pass form, ranges of the span > 1 reduction,
+    // scratch matrices of the span fold, slabs and shares of generation 2, slices of the classic k_fin_Z
+    size_t part_1 = 0, part_e = 0, gpart_fk = 0, red_e = 0, fall = 0, ek_slabs = 0;
+    int nsh = 1, nsl = 1;
+};
+
+// What the construction cuts for the statistics kernels (smcpp_im::cut_stats_layout: no HIP call): the sorted row permutations, the
+// slabs over them, the ranges the reductions walk, the teams, and the sizes that belong to the same cut.  Every list with its device
+// twin; upload() is the one place that copies them.  DESIGN.md section 5: field, decided from, switch.
+template <class T> struct HostDev { std::vector<T> h; DevBuf<T> d; };
+struct StatsLayout {
+    long long n_1_rows = 0, n_e_rows = 0, pieces = 0;   // rows of span 1 / span > 1; pieces of at most 64 positions the latter fall into
+    int slab_rows_1 = 0, slab_rows_e = 0;  // rows per span-1 rank slab / per span > 1 slab
+    bool teams = false;                    // the slab count was aimed at one partial per team of four (SMCPP_STATS_TEAM at construction)
+    int ZS = 8;                            // shares of the cross-slab reduction of the span-1 rank partials
+    int ZG = 1;                            // shares of the per-key gamma-sum reduction of the one-pass span-1 form (a hot key holds most slabs)
+    int llblk = 64;                        // blocks per contig of the log-likelihood reduction
+    HostDev<int> perm1, perme;             // sorted permutations: span-1 rows by (contig, key), span > 1 rows by (contig, eigen key, group)
+    HostDev<int2> perm1k;                  // span-1 rows in natural order: {ell, key id} (one load resolves both)
+    HostDev<Slab> slabs_sc, slabs_rk, slabs_eg;   // span-1 scalar slabs, span-1 rank slabs, eigen slabs
+    HostDev<int> gk_slab_off, s1_slab_off, eb_slab_off, eb_gid, ce_bucket_off, erow_slab;
+    std::vector<int> ce_row_off;           // [n_contigs*Ke + 1] first position in perme of every (contig, eigen key) (host only)
+    // fused span-1 statistics (M <= 64): single-key slabs over the key-sorted span-1 rows (perm1), with their ranges per contig
+    // (rank partials) and per (contig, key) (gamma partials)
+    HostDev<Slab> slabs_fk;
+    HostDev<int> fk_c_off, fk_gk_off;
+    // teams: up to four consecutive slabs of ONE reduction range share a workgroup of k_rank_acc<., true> and one partial
+    HostDev<int2> teams_fk, teams_eg, teams_rk;
+    HostDev<int> fk_c_team_off, eb_team_off, s1_team_off;
+    // generation-2 eigen statistics (M <= 64): slabs over the sorted eigen rows of a (contig, eigen key) that MIX span groups
+    HostDev<Slab> slabs_ek;
+    HostDev<int> ek_slab_off, epos_gid;
+    HostDev<int4> erow_desc;               // per sorted eigen-row position: {row low / high word, group, span} (k_gamma_rows_b)
+    void upload(hipStream_t s) {
+        auto up = [s](auto &...x) { (x.d.upload(x.h, s), ...); };
+        up(slabs_sc, slabs_rk, slabs_eg, perm1, perm1k, perme, gk_slab_off, s1_slab_off, eb_slab_off, eb_gid, ce_bucket_off, erow_slab, slabs_ek,
+           slabs_fk, fk_c_off, fk_gk_off, teams_fk, teams_eg, fk_c_team_off, eb_team_off, teams_rk, s1_team_off, ek_slab_off, epos_gid, erow_desc);
+    }
+};
+
+// save_gamma's long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp): the pieces, their
+// tiles, the first piece of every row - built on first use - and the scratch of their kernels
+struct GammaPieces {
+    bool built = false;
+    HostDev<GPiece> pieces; HostDev<GTile> tiles; HostDev<int> pfirst;
+    DevBuf<float> pvf; DevBuf<double> pvb, pgam, cs, l2d, gen;
 };
 
 // How the chain phase is arranged for one manager and one chunking, resolved from the host layout, the switches and the device's
@@ -116,33 +163,10 @@ struct smcpp_im {
     std::vector<Chunk> chunks;
     int max_chunks_per_contig = 1;
     int user_rows_per_chunk = 0;
-    // sorted permutations and slabs
-    std::vector<int> perm1, perme;
-    std::vector<int2> perm1k;
-    std::vector<Slab> slabs_sc, slabs_rk, slabs_eg;   // span-1 scalar slabs, span-1 rank slabs, eigen slabs
-    std::vector<int> gk_slab_off, s1_slab_off, eb_slab_off, eb_gid, ce_bucket_off, erow_slab;
-    // fused span-1 statistics (M <= 64): single-key slabs over the key-sorted span-1 rows (perm1), with their ranges per contig
-    // (rank partials) and per (contig, key) (gamma partials)
-    std::vector<Slab> slabs_fk;
-    std::vector<int> fk_c_off, fk_gk_off;
-    DevBuf<Slab> d_slabs_fk;
-    DevBuf<int> d_fk_c_off, d_fk_gk_off;
-    DevBuf<double> d_gpart_fk;
-    // teams (round 5): up to four consecutive slabs of ONE reduction range share a workgroup of k_rank_acc<., true> and one partial
-    std::vector<int2> teams_fk, teams_eg, teams_rk;
-    std::vector<int> fk_c_team_off, eb_team_off, s1_team_off;
-    DevBuf<int2> d_teams_fk, d_teams_eg, d_teams_rk;
-    DevBuf<int> d_fk_c_team_off, d_eb_team_off, d_s1_team_off;
-    // generation-2 eigen statistics (M <= 64): slabs over the sorted eigen rows of a (contig, eigen key) that MIX span groups
-    std::vector<Slab> slabs_ek;
-    std::vector<int> ek_slab_off, epos_gid;
-    std::vector<int4> erow_desc;           // per sorted eigen-row position: {row low / high word, group, span} (k_gamma_rows_b)
-    DevBuf<int4> d_erow_desc;
-    DevBuf<Slab> d_slabs_ek;
-    DevBuf<int> d_ek_slab_off, d_epos_gid;
-    DevBuf<double> d_part_ek, d_red_ek;
-    std::vector<int> ce_row_off;           // [n_contigs*Ke + 1] first position in perme of every (contig, eigen key)
-    long long n_e_rows = 0, n_1_rows = 0;
+    StatsLayout lay;                       // sorted permutations, slabs, ranges, teams and sizes of the statistics (cut_stats_layout)
+    GammaPieces gp;
+    StatsLayout cut_stats_layout() const;
+    void build_gamma_pieces();
     // ---- parameters -------------------------------------------------------------------------------------------
     double theta = NAN, rho = NAN, alpha = 1.0;
     bool have_raw = false, dirty = true, params_fresh = false;
@@ -177,6 +201,7 @@ struct smcpp_im {
     };
     hipEvent_t ev[EV_COUNT];
     int dual_stream = 1;
+    void read_dual_stream() { dual_stream = opt().i(smcpp_opt::O_DUAL_STREAM, 1); }      // (build_device; a host-only manager's hook)
     bool chains_dual = false;
     DevBuf<RowInfo> d_rowinfo;
     DevBuf<int2> d_rowdesc;
@@ -364,22 +389,8 @@ struct smcpp_im {
     int score_check(int c);                       // throws unless a score call can run on contig c; -> checkpoint vectors per wavefront
     void score_tables();                          // -> d_sc_tab (keeps E_on_dev: a later smcpp_q stays on its device route)
     const double *score_rows(int c, long long start, long long step, long long ncols, int parts, int nck);   // -> device, on `stream`
-    // per-row posteriors of long rows at 64 < M <= 256 from eigen-power pieces (chains_ss.hpp: k_piece_vectors; engine_plans.hpp)
-    std::vector<GPiece> gp_pieces;
-    std::vector<GTile> gp_tiles;
-    std::vector<int> gp_pfirst;
-    bool gp_built = false;
-    DevBuf<GPiece> d_gp_pieces;
-    DevBuf<GTile> d_gp_tiles;
-    DevBuf<int> d_gp_pfirst;
-    DevBuf<float> d_gp_pvf;
-    DevBuf<double> d_gp_pvb, d_gp_pgam, d_gp_cs, d_gp_l2d, d_gp_gen;
-    long long gp_count = -1;
-    long long gamma_piece_count();         // pieces of at most 64 positions the eigen rows fall into
-    void build_gamma_pieces();
     bool ss_generators_only();             // the generators of T into ss_gen / ss_c0 (no underflow bound: the walks rescale every step)
     DevBuf<float> d_gpark;                 // k_gamma_rows_scan: [wavefronts][max span][64 NPL] parked forward vectors
-    DevBuf<double> d_Fall;                 // [n_contigs Ke][smax][Mp][Mp] scratch of the span fold for M > 64 (k_span_big)
     SsArgs ss_args;
     std::vector<Chunk> chunks_b;           // backward chunks of the scan chains (more and shorter than the forward ones)
     std::vector<int> ss_tasks;             // (direction << 30 | chunk) per wavefront of a k_chain_ss launch
@@ -412,15 +423,15 @@ struct smcpp_im {
     BigArgs pre_bargs;
     std::vector<std::unique_ptr<smcpp_host::EigTeam>> eig_teams;    // team-parallel eigensolver (M >= 128), one team per eigen key
     DevBuf<Chunk> d_chunks;
-    DevBuf<Slab> d_slabs_sc, d_slabs_rk, d_slabs_eg;
-    DevBuf<int2> d_perm1k;                 // span-1 rows sorted by key: {ell, key id} (one load resolves both)
-    DevBuf<int> d_perm1, d_perme, d_gk_slab_off, d_s1_slab_off, d_eb_slab_off, d_eb_gid, d_ce_bucket_off,
-        d_erow_slab, d_g_span, d_g_eig, d_e_kid, d_contig_L, d_changed_f, d_changed_b, d_argmax;
+    DevBuf<int> d_g_span, d_g_eig, d_e_kid, d_contig_L, d_changed_f, d_changed_b, d_argmax;
     DevBuf<long long> d_contig_base;
     DevBuf<float> d_pi_f, d_Tf, d_alpha, d_ends_f, d_used_f;
     DevBuf<double> d_E, d_dpow, d_PinvT, d_PT, d_TdT, d_Td, d_Prm, d_Pinvrm, d_dsc, d_dun, d_g_scale,
         d_g_logscale, d_beta, d_cnorm, d_logc, d_ends_b, d_used_b, d_llpart, d_loglik, d_w1, d_gpart, d_Xs, d_Ys,
-        d_part_e, d_part_1, d_red_e, d_red_1, d_red_g, d_Z, d_Zpart, d_Y, d_xisum, d_gsum, d_gamma0, d_gamma_rows, d_Sq;
+        d_red_1, d_red_g, d_Z, d_Y, d_xisum, d_gsum, d_gamma0, d_gamma_rows, d_Sq;
+    // sized from the plan of an E-step, by size_stats_buffers() alone (d_Fall: [n_contigs Ke][smax][Mp][Mp] scratch of the span fold)
+    DevBuf<double> d_part_1, d_gpart_fk, d_part_e, d_red_e, d_part_ek, d_red_ek, d_Zpart, d_Fall;
+    void size_stats_buffers(const StatsPlan &p);
     // opt-in warm start: chunk-boundary vectors of the previous converged E-step (see smcpp_set_warm_start)
     bool warm_start = false, warm_valid = false;
     DevBuf<float> d_warm_f;
@@ -451,10 +462,6 @@ struct smcpp_im {
     double *h_ll = nullptr;       // pinned: per-contig log-likelihoods
     int h_flags_cap = 0, h_ll_cap = 0;
     size_t param_cap = 0;
-    int llblk = 64;
-    int ZS = 8;
-    int ZG = 1;                          // shares of the per-key gamma-sum reduction of the one-pass span-1 form (a hot key holds most slabs)
-    int slab_rows_1 = 0, slab_rows_e = 0;   // rows per span-1 rank slab / per span > 1 slab as make_slabs cut them (smcpp_describe)
     int last_fwd_passes = 0, last_bwd_passes = 0;
     float eps_f = 2e-6f;
     double eps_b = 1e-6;   // relative; beta only enters products with the float alpha (noise floor 2e-6), see DESIGN.md §3
@@ -499,7 +506,6 @@ struct smcpp_im {
     void build_device(int dev);
     // the plan of this chunking (user_rows_per_chunk) and its chunk lists; a re-plan (smcpp_set_chunking) keeps what is per manager
     void make_chunks() { plan = resolve_chain_plan(cu_count, plan.resolved ? &plan : nullptr); cut_chunks(plan); }
-    void make_slabs();
     void alloc_device();
     void host_prep_and_upload();
     void stage_static_and_prepass();
@@ -513,7 +519,12 @@ struct smcpp_im {
     void finish_stats();
     bool stats_enqueued = false;
     StatsPlan stats_plan;        // of the last enqueue_stats()
-    StatsPlan resolve_stats_plan();
+    StatsPlan resolve_stats_plan(bool generators) const;
+    // save_gamma's long rows at 64 < M <= 256 may take the eigen-power pieces, if generators of T exist (the resolver's `generators`)
+    bool gamma_pieces_fit() const {
+        return save_gamma && lay.n_e_rows > 0 && !estep_route.eigfree && NT > 4 && Mp <= 256 && !opt().off(smcpp_opt::O_GAMMA_PIECES) &&
+               (double)lay.pieces * Mp * 20.0 < 96e9;
+    }
     // (enqueue_stats' helpers and branch launchers)
     hipStream_t plan_stream(StatsPlan::Stream x) const {
         return x == StatsPlan::SECOND ? stream2 : x == StatsPlan::THIRD ? stream3 : x == StatsPlan::HIGH ? stream_hi : stream;
@@ -522,7 +533,7 @@ struct smcpp_im {
     void hand_over(Ev e, hipStream_t from, hipStream_t to) { HIPCHK(hipEventRecord(ev[e], from)); HIPCHK(hipStreamWaitEvent(to, ev[e], 0)); }
     void fork_from_chains(hipStream_t x);
     S1Args s1_args(bool span_gt1);
-    AccArgs acc_args(const std::vector<Slab> &sl, const Slab *d_sl, const int *perm, const int2 *permk, double *part, double *gpart);
+    AccArgs acc_args(const HostDev<Slab> &sl, const int *perm, const int2 *permk, double *part, double *gpart);
     void launch_span_gt1_rank(const StatsPlan &p), launch_span1_branch(const StatsPlan &p), launch_gamma_rows(const StatsPlan &p);
     void launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa);
     void estep();
@@ -739,7 +750,7 @@ void smcpp_im::build_device(int dev) {
         HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
         HIPCHK(hipStreamCreateWithPriority(&stream_hi, hipStreamNonBlocking, greatest));
     }
-    if (opt().has(smcpp_opt::O_DUAL_STREAM)) dual_stream = opt().i(smcpp_opt::O_DUAL_STREAM, 1);
+    read_dual_stream();
     {
         // The events order streams of this device and bracket intervals; nothing the host reads depends on a system-scope fence at
         // an event (results reach it through stream-ordered copies and the pinned completion word of k_signal / k_fin_both).  A
@@ -754,7 +765,7 @@ void smcpp_im::build_device(int dev) {
         cu_count = prop.multiProcessorCount;
     }
     make_chunks();
-    make_slabs();
+    lay = cut_stats_layout();
     alloc_device();
     update_pi_default();
     // defaults after construction (_smcpp.pyx:318-320)
@@ -1169,26 +1180,32 @@ void smcpp_im::update_pi_default() {
 
 static bool stats_team_on() { return !opt().off(smcpp_opt::O_STATS_TEAM); }
 
-void smcpp_im::make_slabs() {
+// The layout of the statistics: reads the row layout (rowinfo, groups, contig_base, Ls, the shape) and the switches SMCPP_SLAB_ROWS and
+// SMCPP_STATS_TEAM, writes nothing else, calls no HIP function: smcpp_host_stats_plan runs it on a machine without a device.
+StatsLayout smcpp_im::cut_stats_layout() const {
+    StatsLayout L;
+    auto &perm1 = L.perm1.h, &perme = L.perme.h, &gk_slab_off = L.gk_slab_off.h, &s1_slab_off = L.s1_slab_off.h, &eb_slab_off = L.eb_slab_off.h,
+         &eb_gid = L.eb_gid.h, &ce_bucket_off = L.ce_bucket_off.h, &ce_row_off = L.ce_row_off, &erow_slab = L.erow_slab.h, &fk_c_off = L.fk_c_off.h,
+         &fk_gk_off = L.fk_gk_off.h, &ek_slab_off = L.ek_slab_off.h, &epos_gid = L.epos_gid.h;
+    auto &perm1k = L.perm1k.h; auto &erow_desc = L.erow_desc.h;
+    auto &slabs_sc = L.slabs_sc.h, &slabs_rk = L.slabs_rk.h, &slabs_eg = L.slabs_eg.h, &slabs_fk = L.slabs_fk.h, &slabs_ek = L.slabs_ek.h;
     // counting sorts of rows per contig
-    perm1.clear(); perme.clear(); perm1k.clear();
-    slabs_sc.clear(); slabs_rk.clear(); slabs_eg.clear();
     gk_slab_off.assign((size_t)n_contigs * K + 1, 0);
     s1_slab_off.assign(n_contigs + 1, 0);
     ce_bucket_off.assign((size_t)n_contigs * Ke + 1, 0);
     ce_row_off.assign((size_t)n_contigs * Ke + 1, 0);
-    eb_slab_off.clear(); eb_gid.clear(); erow_slab.clear();
     int last_eig_key = -1;
     long long n1 = 0, ne = 0;
     // (rows with ell = 0 have kid = 0, gid = -1 and are skipped below)
     for (int c = 0; c < n_contigs; ++c)
         for (int i = 1; i <= Ls[c]; ++i) (rowinfo[(size_t)contig_base[c] + i].gid < 0 ? n1 : ne)++;
-    n_1_rows = n1; n_e_rows = ne;
+    L.n_1_rows = n1; L.n_e_rows = ne;
     const long long part_bytes = (long long)Mp * Mp * 8;
     // slabs = independent single-wavefront work items; several thousand keep the 2048 resident wavefronts of the
     // chip balanced on large inputs (each slab owns an Mp x Mp partial: at most 256 MB of them)
     // (round 5: teams of four slabs share one partial - k_rank_acc<., true> -, so four times as many slabs fit the same 256 MB)
-    const long long target = std::max<long long>(256, std::min<long long>(8192, ((stats_team_on() ? 1024ll : 256ll) << 20) / part_bytes));
+    L.teams = stats_team_on();
+    const long long target = std::max<long long>(256, std::min<long long>(8192, ((L.teams ? 1024ll : 256ll) << 20) / part_bytes));
     // (at least SMCPP_SLAB_ROWS rows per slab, default 128: every slab costs an Mp x Mp partial written and read back - 128 MB of
     // traffic per headline E-step with 64-row slabs -, but a slab is walked by ONE wavefront, and below ~1000 slabs the rank
     // kernels leave SIMDs idle: 64 .. 192 rows measured: 633 / 641 / 666 / 665 headline evals per second)
@@ -1198,7 +1215,7 @@ void smcpp_im::make_slabs() {
     int S_EG = (int)std::max<long long>(slab_rows, (ne + target - 1) / target);
     S_EG = (S_EG + 15) / 16 * 16;
     const int S_SC = 256;
-    slab_rows_1 = S_RK; slab_rows_e = S_EG;
+    L.slab_rows_1 = S_RK; L.slab_rows_e = S_EG;
     for (int c = 0; c < n_contigs; ++c) {
         const long long base = contig_base[c];
         // ---- span-1 rows sorted by key ----
@@ -1262,7 +1279,6 @@ void smcpp_im::make_slabs() {
     ce_row_off[(size_t)n_contigs * Ke] = (int)perme.size();
     eb_slab_off.push_back((int)slabs_eg.size());
     // single-key span-1 slabs in key-sorted order (k_rank_acc<3>)
-    slabs_fk.clear();
     fk_c_off.assign(n_contigs + 1, 0);
     fk_gk_off.assign((size_t)n_contigs * K + 1, 0);
     for (int c = 0; c < n_contigs; ++c) {
@@ -1287,22 +1303,21 @@ void smcpp_im::make_slabs() {
             }
             if (!range_off.empty()) team_off.back() = (int)teams.size();
         };
-        cut(fk_c_off, teams_fk, fk_c_team_off);
-        cut(eb_slab_off, teams_eg, eb_team_off);
-        cut(s1_slab_off, teams_rk, s1_team_off);
+        cut(fk_c_off, L.teams_fk.h, L.fk_c_team_off.h);
+        cut(eb_slab_off, L.teams_eg.h, L.eb_team_off.h);
+        cut(s1_slab_off, L.teams_rk.h, L.s1_team_off.h);
     }
     // generation-2 eigen slabs: the sorted eigen rows of every (contig, eigen key) cut into S_EG-row pieces regardless of the span
     // groups; padded like slabs_eg so that a workgroup of four never mixes keys
-    slabs_ek.clear(); epos_gid.clear();
     ek_slab_off.assign((size_t)n_contigs * Ke + 1, 0);
     epos_gid.reserve(perme.size());
     for (size_t q = 0; q < erow_slab.size(); ++q) epos_gid.push_back(slabs_eg[erow_slab[q]].aux);
-    erow_desc.clear();
     erow_desc.reserve(perme.size());
     for (size_t q = 0; q < erow_slab.size(); ++q) {
         const Slab &sl = slabs_eg[erow_slab[q]];
         const long long row = sl.base + perme[q];
         erow_desc.push_back(make_int4((int)(row & 0xffffffffll), (int)(row >> 32), sl.aux, groups[sl.aux].span));
+        L.pieces += (groups[sl.aux].span + 63) / 64;             // (the eigen-power pieces of save_gamma: at most 64 positions each)
     }
     for (int c = 0; c < n_contigs; ++c)
         for (int e = 0; e < Ke; ++e) {
@@ -1315,6 +1330,18 @@ void smcpp_im::make_slabs() {
     // (a padding slab sits in front of the first slab of the next key: it belongs to the PREVIOUS (contig, key)'s range only if
     // that range is recorded after it, so ranges are closed here, over the padded list)
     ek_slab_off[(size_t)n_contigs * Ke] = (int)slabs_ek.size();
+    {
+        // blocks per contig of the log-likelihood reduction: ~2 000 rows each (64 blocks took 0.13 ms on a contig of a million rows)
+        int maxL = 0;
+        for (int c = 0; c < n_contigs; ++c) maxL = std::max(maxL, Ls[c]);
+        L.llblk = std::max(64, std::min(1024, (maxL + 2047) / 2048));
+    }
+    // shares of the cross-slab reduction of the span-1 rank partials: few contigs, small M -> more, shorter shares (one contig at M = 64:
+    // 8 shares of 126 slabs took 38 us of dependent loads)
+    L.ZS = (int)std::max<long long>(8, std::min<long long>(16, 2048 / std::max<long long>(1, (long long)n_contigs * ceil_div((long long)Mp * Mp, 256))));
+    // (the monomorphic key alone holds half the span-1 slabs of a contig: one block walking them took 42 us on the headline)
+    L.ZG = (int)std::max<long long>(1, std::min<long long>(16, 1024 / std::max<long long>(1, (long long)n_contigs * K)));
+    return L;
 }
 
 // the operand buffers of the eigen-free pre-pass, where the plan takes it (ChainPlan::power_ok)
@@ -1377,31 +1404,7 @@ void smcpp_im::alloc_device() {
         }
     }
     upload_chunk_state();
-    d_slabs_sc.upload(slabs_sc, s);
-    d_slabs_rk.upload(slabs_rk, s);
-    d_slabs_eg.upload(slabs_eg, s);
-    d_perm1.upload(perm1, s);
-    d_perm1k.upload(perm1k, s);
-    d_perme.upload(perme, s);
-    d_gk_slab_off.upload(gk_slab_off, s);
-    d_s1_slab_off.upload(s1_slab_off, s);
-    d_eb_slab_off.upload(eb_slab_off, s);
-    d_eb_gid.upload(eb_gid, s);
-    d_ce_bucket_off.upload(ce_bucket_off, s);
-    d_erow_slab.upload(erow_slab, s);
-    d_slabs_ek.upload(slabs_ek, s);
-    d_slabs_fk.upload(slabs_fk, s);
-    d_fk_c_off.upload(fk_c_off, s);
-    d_fk_gk_off.upload(fk_gk_off, s);
-    d_teams_fk.upload(teams_fk, s);
-    d_teams_eg.upload(teams_eg, s);
-    d_fk_c_team_off.upload(fk_c_team_off, s);
-    d_eb_team_off.upload(eb_team_off, s);
-    d_teams_rk.upload(teams_rk, s);
-    d_s1_team_off.upload(s1_team_off, s);
-    d_ek_slab_off.upload(ek_slab_off, s);
-    d_epos_gid.upload(epos_gid, s);
-    d_erow_desc.upload(erow_desc, s);
+    lay.upload(s);
     d_contig_base.upload(contig_base, s);
     d_contig_L.upload(Ls, s);
     std::vector<int> gs(G), ge(G);
@@ -1415,28 +1418,15 @@ void smcpp_im::alloc_device() {
     d_cnorm.alloc((size_t)total_rows);
     d_logc.alloc((size_t)total_rows);
     d_w1.alloc((size_t)total_rows);
-    {
-        // blocks per contig of the log-likelihood reduction: ~2 000 rows each (64 blocks took 0.13 ms on a contig of a million rows)
-        int maxL = 0;
-        for (int c = 0; c < n_contigs; ++c) maxL = std::max(maxL, Ls[c]);
-        llblk = std::max(64, std::min(1024, (maxL + 2047) / 2048));
-    }
-    d_llpart.alloc((size_t)n_contigs * llblk);
+    d_llpart.alloc((size_t)n_contigs * lay.llblk);
     d_loglik.alloc(n_contigs);
-    d_gpart.alloc(std::max<size_t>(1, slabs_sc.size()) * Mp);
+    d_gpart.alloc(std::max<size_t>(1, lay.slabs_sc.h.size()) * Mp);
     // omega*U and W of the eigen rows only go through memory when the fused kernel cannot be used (M > 64)
-    d_Xs.alloc(NT <= 4 ? 1 : std::max<size_t>(1, (size_t)n_e_rows) * Mp);
-    d_Ys.alloc(NT <= 4 ? 1 : std::max<size_t>(1, (size_t)n_e_rows) * Mp);
-    // (d_part_e / d_red_e - one M x M partial per span GROUP slab / bucket - are allocated where they are used: un-binned data have
-    // 10^5 groups and never take those paths when M <= 64)
-    d_part_1.alloc(std::max<size_t>(1, stats_team_on() ? teams_rk.size() : slabs_rk.size()) * Mp * Mp);      // (one partial per team)
-    // shares of the cross-slab reduction of the span-1 rank partials: few contigs, small M -> more, shorter shares (one contig at M = 64:
-    // 8 shares of 126 slabs took 38 us of dependent loads)
-    ZS = (int)std::max<long long>(8, std::min<long long>(16, 2048 / std::max<long long>(1, (long long)n_contigs * ceil_div((long long)Mp * Mp, 256))));
-    d_red_1.alloc((size_t)n_contigs * ZS * Mp * Mp);
-    // (the monomorphic key alone holds half the span-1 slabs of a contig: one block walking them took 42 us on the headline)
-    ZG = (int)std::max<long long>(1, std::min<long long>(16, 1024 / std::max<long long>(1, (long long)n_contigs * K)));
-    d_red_g.alloc((size_t)n_contigs * K * Mp * ZG);
+    d_Xs.alloc(NT <= 4 ? 1 : std::max<size_t>(1, (size_t)lay.n_e_rows) * Mp);
+    d_Ys.alloc(NT <= 4 ? 1 : std::max<size_t>(1, (size_t)lay.n_e_rows) * Mp);
+    // (what follows from an E-step's plan is sized there, size_stats_buffers: un-binned data have 10^5 span groups and never take the per-group paths at M <= 64)
+    d_red_1.alloc((size_t)n_contigs * lay.ZS * Mp * Mp);
+    d_red_g.alloc((size_t)n_contigs * K * Mp * lay.ZG);
     d_Z.alloc(std::max<size_t>(1, (size_t)n_contigs * Ke) * Mp * Mp);
     d_Y.alloc(std::max<size_t>(1, (size_t)n_contigs * Ke) * Mp * Mp);
     d_xisum.alloc((size_t)n_contigs * Mp * Mp);

@@ -796,10 +796,11 @@ void smcpp_im::finish_stats() {
 // ---- statistics: one plan per enqueue (resolve_stats_plan), then branch launchers that only read it ----
 // One rank update: k_rank_acc_wide (operand rows staged through LDS; modes 0 / 2), k_rank_acc over teams of up to four slabs of one
 // reduction range that add their accumulators through LDS (teams != nullptr), or k_rank_acc with one wavefront per slab
+// (nparts: partials the launch writes - teams, or slabs where teams == nullptr: StatsPlan::part_1 / part_e)
 template <int MODE>
-static void launch_rank_acc(AccArgs a, bool wide, const int2 *teams, size_t nteams, hipStream_t s) {
+static void launch_rank_acc(AccArgs a, bool wide, const int2 *teams, size_t nparts, hipStream_t s) {
     a.teams = teams;
-    const unsigned nx = teams ? (unsigned)nteams : (unsigned)a.nslabs, ny = MODE == 3 ? 1u : (unsigned)(a.NB * a.NB);
+    const unsigned nx = (unsigned)nparts, ny = MODE == 3 ? 1u : (unsigned)(a.NB * a.NB);
     if constexpr (MODE == 0 || MODE == 2) {
         if (wide) {
             lds_limit_once<k_rank_acc_wide<MODE, 8>>();
@@ -820,31 +821,31 @@ static void sum_parts(const double *part, const int *off, double *red, int len, 
 }
 static int fin_blocks(int Mp, int K) { return ceil_div((long long)Mp * Mp, 256) + ceil_div((long long)(K + 1) * Mp, 256); }
 
-StatsPlan smcpp_im::resolve_stats_plan() {
+StatsPlan smcpp_im::resolve_stats_plan(bool generators) const {
     using P = StatsPlan;
     P p;
     p.resolved = true;
     const bool dual = dual_stream != 0;
     // the span > 1 branch (weights, rank update, span fold or U / W products, Y) does not depend on the span-1 branch (weights, rank
     // update, gamma sums): on two streams the short launches of one fill the gaps of the other
-    p.split = dual && !slabs_eg.empty();
+    p.split = dual && !lay.slabs_eg.h.empty();
     // Eigen-free statistics of small inputs: the span > 1 rank update -> reduction -> span fold (2 x s_max serial steps) is the critical
     // path, and a hop between two streams costs ~10 us (2 us between two kernels of one queue): THAT branch keeps the main stream,
     // directly behind the chains and in front of the finalisation, and the span-1 branch (which has slack) forks.  (M > 64: chip-filling
     // rank updates, the hops do not matter and the other order is 3 % faster.)
-    const bool crit_main = estep_route.eigfree && p.split && n_e_rows < 1000000 && Mp <= 64;
+    const bool crit_main = estep_route.eigfree && p.split && lay.n_e_rows < 1000000 && Mp <= 64;
     p.span_gt1 = p.split && !crit_main ? P::SECOND : P::MAIN;
     p.span1 = crit_main ? P::SECOND : P::MAIN;
     // M <= 64, from half a million span-1 rows on: ONE pass over the key-sorted span-1 rows gives the rank update and the key's gamma
     // sums from the same operands (k_rank_acc<3>): whole genome (3.6 M rows, bandwidth-bound) 3.77 -> 3.15 ms of statistics; one 100
     // Mbp contig (129 k rows, latency-bound) 0.208 -> 0.225 ms - there the gamma sums stay a third concurrent branch, unless the span > 1
     // branch holds the main stream: then ONE side branch beats two (887 against 873 evals/s).  SMCPP_S1_FUSE=0 / 1 forces either form.
-    p.s1_one_pass = Mp <= 64 && !save_gamma && !slabs_fk.empty() &&
-                    (opt().has(smcpp_opt::O_S1_FUSE) ? opt().i(smcpp_opt::O_S1_FUSE, 0) != 0 : (n_1_rows >= 500000 || crit_main));
+    p.s1_one_pass = Mp <= 64 && !save_gamma && !lay.slabs_fk.h.empty() &&
+                    (opt().has(smcpp_opt::O_S1_FUSE) ? opt().i(smcpp_opt::O_S1_FUSE, 0) != 0 : (lay.n_1_rows >= 500000 || crit_main));
     // two kernels at M <= 64: k_rank_acc forms the span-1 weights itself, so the per-key gamma sums (k_s1_scalars + reduction) are a
     // third independent branch; else, on two streams, they are reduced at the tail of the span > 1 branch (which finishes earlier)
-    const bool gsum_own = !p.s1_one_pass && dual && Mp <= 64 && !save_gamma && !slabs_sc.empty();
-    p.gsum_at = p.s1_one_pass ? P::GSUM_ONE_PASS : gsum_own ? P::GSUM_OWN_STREAM : p.split && !slabs_sc.empty() ? P::GSUM_SPAN_GT1_TAIL : P::GSUM_SPAN1;
+    const bool gsum_own = !p.s1_one_pass && dual && Mp <= 64 && !save_gamma && !lay.slabs_sc.h.empty();
+    p.gsum_at = p.s1_one_pass ? P::GSUM_ONE_PASS : gsum_own ? P::GSUM_OWN_STREAM : p.split && !lay.slabs_sc.h.empty() ? P::GSUM_SPAN_GT1_TAIL : P::GSUM_SPAN1;
     p.gsum = gsum_own ? P::THIRD : p.span1;
     // nothing in the statistics reads log_c: the log-likelihood runs on the third stream beside both branches (0.1 ms on un-binned
     // data) - unless the span > 1 branch holds the main stream and the gamma sums the third: then at the head of the span-1 branch
@@ -855,19 +856,18 @@ StatsPlan smcpp_im::resolve_stats_plan() {
     // the partial bytes (SMCPP_STATS_TEAM=0: one partial per slab).
     const bool teams = stats_team_on();
     p.rank = Mp > 128 && !opt().off(smcpp_opt::O_RANK_WIDE) ? P::RANK_WIDE : teams ? P::RANK_TEAMS : P::RANK_PER_SLAB;
-    p.teams_span1 = teams && !teams_rk.empty();
-    p.teams_one_pass = teams && !teams_fk.empty();
-    p.teams_span_gt1 = teams && estep_route.eigfree && !teams_eg.empty();
-    if (estep_route.eigfree) p.eigen = slabs_eg.empty() ? P::EIG_NONE : estep_route.ss_active && !opt().off(smcpp_opt::O_SPAN_SCAN) ? P::EIG_FOLD_SCANS : P::EIG_FOLD_MATRIX_CORES;
-    else p.eigen = NT <= 4 && !slabs_eg.empty() ? P::EIG_GEN2 : P::EIG_CLASSIC;
+    p.teams_span1 = teams && !lay.teams_rk.h.empty();
+    p.teams_one_pass = teams && !lay.teams_fk.h.empty();
+    p.teams_span_gt1 = teams && estep_route.eigfree && !lay.teams_eg.h.empty();
+    if (estep_route.eigfree) p.eigen = lay.slabs_eg.h.empty() ? P::EIG_NONE : estep_route.ss_active && !opt().off(smcpp_opt::O_SPAN_SCAN) ? P::EIG_FOLD_SCANS : P::EIG_FOLD_MATRIX_CORES;
+    else p.eigen = NT <= 4 && !lay.slabs_eg.h.empty() ? P::EIG_GEN2 : P::EIG_CLASSIC;
     // the span fold (tens of serial steps on a few CUs) ends the longest dependency chain, so what it waits for goes FIRST and alone
     // (small inputs only: from ~10^6 span > 1 rows on, the two rank updates side by side finish sooner - whole genome 3.76 -> 3.36 ms)
-    p.rank_early = estep_route.eigfree && p.split && n_e_rows < 1000000;
-    if (save_gamma && n_e_rows > 0) {
+    p.rank_early = estep_route.eigfree && p.split && lay.n_e_rows < 1000000;
+    if (save_gamma && lay.n_e_rows > 0) {
         // long rows at 64 < M <= 256 with a structured T: eigen-power pieces + scan steps, which read the statistics' U / W products
         // (main stream, behind them); the other forms need alpha, beta and the eigensystems only: beside the statistics
-        const bool pieces = !estep_route.eigfree && NT > 4 && Mp <= 256 && !opt().off(smcpp_opt::O_GAMMA_PIECES) &&
-                            (double)gamma_piece_count() * Mp * 20.0 < 96e9 && (estep_route.ss_active || ss_generators_only());
+        const bool pieces = gamma_pieces_fit() && generators;
         p.gamma_beside = dual && !pieces && !opt().off(smcpp_opt::O_GAMMA_SIDE);
         p.gamma = p.gamma_beside ? P::HIGH : P::MAIN;
         p.gamma_form = pieces ? P::GAMMA_PIECES : estep_route.eigfree ? P::GAMMA_SCAN : NT <= 4 ? P::GAMMA_EIG_BATCHES : P::GAMMA_EIG_ROWS;
@@ -875,7 +875,40 @@ StatsPlan smcpp_im::resolve_stats_plan() {
     // the finalisation signals the host itself when nothing follows it on the main stream and the launch is small: every block ends
     // with a device-scope fence and an atomic on ONE counter (1 500 contigs: 3.2 ms; beyond 128 blocks the one-thread kernel signals)
     p.fin_signals = !save_gamma && !ll_own && (long long)fin_blocks(Mp, K) * n_contigs <= 128;
+    // ---- counts: what the launches put into their grids and size_stats_buffers() into the buffers ----
+    p.part_1 = p.s1_one_pass ? (p.teams_one_pass ? lay.teams_fk.h.size() : lay.slabs_fk.h.size()) : (p.teams_span1 ? lay.teams_rk.h.size() : lay.slabs_rk.h.size());
+    p.gpart_fk = p.s1_one_pass ? lay.slabs_fk.h.size() : 0;
+    // (one M x M partial per span GROUP slab or team, one reduced matrix per bucket: not for generation 2, whose slabs mix the groups)
+    if (!lay.slabs_eg.h.empty() && p.eigen != P::EIG_GEN2) {
+        p.part_e = p.teams_span_gt1 ? lay.teams_eg.h.size() : lay.slabs_eg.h.size();
+        p.red_e = estep_route.eigfree ? std::max<size_t>(1, lay.eb_gid.h.size()) : 0;
+    }
+    if (p.eigen == P::EIG_FOLD_SCANS || p.eigen == P::EIG_FOLD_MATRIX_CORES) p.fall = (size_t)n_contigs * Ke * ss_max_span;
+    if (p.eigen == P::EIG_GEN2) {
+        p.ek_slabs = lay.slabs_ek.h.size();
+        int max_sl = 1;          // shares of the cross-slab reduction: ~32 slabs each (un-binned data: thousands of slabs on a handful of (contig, key) pairs)
+        for (int ce = 0; ce < n_contigs * Ke; ++ce) max_sl = std::max(max_sl, lay.ek_slab_off.h[ce + 1] - lay.ek_slab_off.h[ce]);
+        p.nsh = std::max(1, std::min(128, (max_sl + 31) / 32));
+    }
+    if (p.eigen == P::EIG_CLASSIC && Ke > 0) {
+        int max_b = 0;           // slices of the groups of one (contig, key): enough blocks to fill the chip when there are many groups
+        for (size_t ce = 0; ce + 1 < lay.ce_bucket_off.h.size(); ++ce) max_b = std::max(max_b, lay.ce_bucket_off.h[ce + 1] - lay.ce_bucket_off.h[ce]);
+        p.nsl = std::max(1, std::min(std::min(256, max_b), 2048 / std::max(1, ceil_div((long long)Mp * Mp, 256) * n_contigs * Ke)));
+    }
     return p;
+}
+
+// The buffers whose size follows from the plan, at the head of the statistics: a steady-state E-step finds them large enough
+void smcpp_im::size_stats_buffers(const StatsPlan &p) {
+    const size_t MM = (size_t)Mp * Mp;
+    d_part_1.alloc(std::max<size_t>(1, p.part_1) * MM);
+    d_gpart_fk.alloc(p.gpart_fk * Mp);
+    if (p.part_e) d_part_e.alloc(p.part_e * MM);
+    d_red_e.alloc(p.red_e * MM);
+    d_Fall.alloc(p.fall * MM);
+    // (generation 2, per slab: the M x M accumulator and the M diagonal sums)
+    if (p.eigen == StatsPlan::EIG_GEN2) { d_part_ek.alloc(std::max<size_t>(1, p.ek_slabs) * (MM + Mp)); d_red_ek.alloc((size_t)n_contigs * Ke * p.nsh * (MM + Mp)); }
+    if (p.nsl > 1) d_Zpart.alloc((size_t)p.nsl * n_contigs * Ke * MM);
 }
 
 // A side stream forks off the chains' end and waits for the parameter arena copied beside them as well: its kernels read the log-scales
@@ -890,19 +923,19 @@ void smcpp_im::fork_from_chains(hipStream_t x) {
 S1Args smcpp_im::s1_args(bool span_gt1) {
     S1Args a;
     a.M = M; a.Mp = Mp;
-    a.nslabs = (int)(span_gt1 ? slabs_eg.size() : slabs_sc.size()); a.slabs = span_gt1 ? d_slabs_eg.p : d_slabs_sc.p;
-    a.perm = span_gt1 ? d_perme.p : d_perm1.p;
+    a.nslabs = (int)(span_gt1 ? lay.slabs_eg.h.size() : lay.slabs_sc.h.size()); a.slabs = span_gt1 ? lay.slabs_eg.d.p : lay.slabs_sc.d.p;
+    a.perm = span_gt1 ? lay.perme.d.p : lay.perm1.d.p;
     a.alpha = d_alpha.p; a.beta = d_beta.p; a.cnorm = d_cnorm.p; a.w1 = d_w1.p; a.gpart = d_gpart.p;
     a.gamma_rows = !span_gt1 && save_gamma ? d_gamma_rows.p : nullptr;
     a.only_w1 = span_gt1 ? 1 : 0;
     return a;
 }
 
-AccArgs smcpp_im::acc_args(const std::vector<Slab> &sl, const Slab *d_sl, const int *perm, const int2 *permk, double *part, double *gpart) {
+AccArgs smcpp_im::acc_args(const HostDev<Slab> &sl, const int *perm, const int2 *permk, double *part, double *gpart) {
     AccArgs a;
     a.M = M; a.Mp = Mp; a.NB = (Mp + 63) / 64; a.rowinfo = d_rowinfo.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
     a.w1 = d_w1.p; a.cnorm = d_cnorm.p; a.E = d_E.p; a.Xs = d_Xs.p; a.Ys = d_Ys.p;
-    a.nslabs = (int)sl.size(); a.slabs = d_sl; a.perm = perm; a.permk = permk; a.part = part; a.gpart = gpart; a.teams = nullptr;
+    a.nslabs = (int)sl.h.size(); a.slabs = sl.d.p; a.perm = perm; a.permk = permk; a.part = part; a.gpart = gpart; a.teams = nullptr;
     return a;
 }
 
@@ -910,8 +943,8 @@ AccArgs smcpp_im::acc_args(const std::vector<Slab> &sl, const Slab *d_sl, const 
 void smcpp_im::launch_span_gt1_rank(const StatsPlan &p) {
     const hipStream_t se = plan_stream(p.span_gt1);
     if (Mp > 64) launch_s1(NPL, s1_args(true), se);
-    launch_rank_acc<2>(acc_args(slabs_eg, d_slabs_eg.p, d_perme.p, nullptr, d_part_e.p, nullptr), p.rank == StatsPlan::RANK_WIDE,
-                       p.teams_span_gt1 ? d_teams_eg.p : nullptr, teams_eg.size(), se);
+    launch_rank_acc<2>(acc_args(lay.slabs_eg, lay.perme.d.p, nullptr, d_part_e.p, nullptr), p.rank == StatsPlan::RANK_WIDE,
+                       p.teams_span_gt1 ? lay.teams_eg.d.p : nullptr, p.part_e, se);
 }
 
 void smcpp_im::launch_span1_branch(const StatsPlan &p) {
@@ -921,10 +954,10 @@ void smcpp_im::launch_span1_branch(const StatsPlan &p) {
         if (p.span1 == StatsPlan::SECOND) fork_from_chains(stream3);     // (forks where the span-1 branch does)
         else hand_over(EV_GSUM_FORK, stream, stream3);
     }
-    if (!p.s1_one_pass && !slabs_sc.empty()) {
+    if (!p.s1_one_pass && !lay.slabs_sc.h.empty()) {
         launch_s1(NPL, s1_args(false), sg1);
         if (p.gsum_at == StatsPlan::GSUM_OWN_STREAM) {
-            sum_parts(d_gpart.p, d_gk_slab_off.p, d_red_g.p, Mp, n_contigs * K, 1, sg1);
+            sum_parts(d_gpart.p, lay.gk_slab_off.d.p, d_red_g.p, Mp, n_contigs * K, 1, sg1);
             HIPCHK(hipEventRecord(ev[EV_GSUM_DONE], sg1));
         } else if (p.gsum_at == StatsPlan::GSUM_SPAN_GT1_TAIL) HIPCHK(hipEventRecord(ev[EV_S1_SCALARS], sp1));
     }
@@ -932,18 +965,16 @@ void smcpp_im::launch_span1_branch(const StatsPlan &p) {
     // starts - its weights pass (k_s1_scalars, bound by memory round trips) runs beside the head of that rank update
     if (p.rank_early && p.span1 == StatsPlan::MAIN) HIPCHK(hipStreamWaitEvent(sp1, ev[EV_RANK2_DONE], 0));
     if (p.s1_one_pass) {
-        d_part_1.alloc(std::max<size_t>(1, p.teams_one_pass ? teams_fk.size() : slabs_fk.size()) * Mp * Mp);
-        d_gpart_fk.alloc(slabs_fk.size() * Mp);
-        launch_rank_acc<3>(acc_args(slabs_fk, d_slabs_fk.p, d_perm1.p, nullptr, d_part_1.p, d_gpart_fk.p), false,
-                           p.teams_one_pass ? d_teams_fk.p : nullptr, teams_fk.size(), sp1);
-        sum_parts(d_gpart_fk.p, d_fk_gk_off.p, d_red_g.p, Mp, n_contigs * K, ZG, sp1);
-        sum_parts(d_part_1.p, p.teams_one_pass ? d_fk_c_team_off.p : d_fk_c_off.p, d_red_1.p, MMi, n_contigs, ZS, sp1);
+        launch_rank_acc<3>(acc_args(lay.slabs_fk, lay.perm1.d.p, nullptr, d_part_1.p, d_gpart_fk.p), false,
+                           p.teams_one_pass ? lay.teams_fk.d.p : nullptr, p.part_1, sp1);
+        sum_parts(d_gpart_fk.p, lay.fk_gk_off.d.p, d_red_g.p, Mp, n_contigs * K, lay.ZG, sp1);
+        sum_parts(d_part_1.p, p.teams_one_pass ? lay.fk_c_team_off.d.p : lay.fk_c_off.d.p, d_red_1.p, MMi, n_contigs, lay.ZS, sp1);
     } else {
-        if (!slabs_rk.empty())
-            launch_rank_acc<0>(acc_args(slabs_rk, d_slabs_rk.p, d_perm1.p, d_perm1k.p, d_part_1.p, nullptr), p.rank == StatsPlan::RANK_WIDE,
-                               p.teams_span1 ? d_teams_rk.p : nullptr, teams_rk.size(), sp1);
-        if (p.gsum_at == StatsPlan::GSUM_SPAN1) sum_parts(d_gpart.p, d_gk_slab_off.p, d_red_g.p, Mp, n_contigs * K, 1, sp1);
-        sum_parts(d_part_1.p, p.teams_span1 ? d_s1_team_off.p : d_s1_slab_off.p, d_red_1.p, MMi, n_contigs, ZS, sp1);
+        if (!lay.slabs_rk.h.empty())
+            launch_rank_acc<0>(acc_args(lay.slabs_rk, lay.perm1.d.p, lay.perm1k.d.p, d_part_1.p, nullptr), p.rank == StatsPlan::RANK_WIDE,
+                               p.teams_span1 ? lay.teams_rk.d.p : nullptr, p.part_1, sp1);
+        if (p.gsum_at == StatsPlan::GSUM_SPAN1) sum_parts(d_gpart.p, lay.gk_slab_off.d.p, d_red_g.p, Mp, n_contigs * K, 1, sp1);
+        sum_parts(d_part_1.p, p.teams_span1 ? lay.s1_team_off.d.p : lay.s1_slab_off.d.p, d_red_1.p, MMi, n_contigs, lay.ZS, sp1);
     }
     HIPCHK(hipEventRecord(ev[EV_SPAN1_DONE], sp1));
 }
@@ -958,9 +989,8 @@ void smcpp_im::launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa) {
         // weights and rank update per (span, key) group (unless launched early), deterministic reduction of the slab partials, then
         // the span fold per (contig, key)
         if (!p.rank_early) launch_span_gt1_rank(p);
-        if (!eb_gid.empty())                                     // ONE share per bucket: k_span_F reads it on its serial path
-            sum_parts(d_part_e.p, p.teams_span_gt1 ? d_eb_team_off.p : d_eb_slab_off.p, d_red_e.p, MMi, (unsigned)eb_gid.size(), 1, se);
-        d_Fall.alloc((size_t)n_contigs * Ke * ss_max_span * Mp * Mp);
+        if (!lay.eb_gid.h.empty())                                     // ONE share per bucket: k_span_F reads it on its serial path
+            sum_parts(d_part_e.p, p.teams_span_gt1 ? lay.eb_team_off.d.p : lay.eb_slab_off.d.p, d_red_e.p, MMi, (unsigned)lay.eb_gid.h.size(), 1, se);
         if (p.eigen == StatsPlan::EIG_FOLD_SCANS) {
             // a row of F times A / A times a column of H is one O(M) step of the backward / forward chain operator, so one wavefront
             // per row / column walks all s_max steps on its own - no matrix product, no barrier
@@ -986,18 +1016,12 @@ void smcpp_im::launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa) {
     case StatsPlan::EIG_GEN2: {
         // slabs that mix span groups, the span-Q weighting inside the accumulation
         UWArgs ua;
-        ua.M = M; ua.Mp = Mp; ua.nslabs = (int)slabs_ek.size(); ua.slabs = d_slabs_ek.p; ua.perm = d_perme.p;
+        ua.M = M; ua.Mp = Mp; ua.nslabs = (int)p.ek_slabs; ua.slabs = lay.slabs_ek.d.p; ua.perm = lay.perme.d.p;
         ua.alpha = d_alpha.p; ua.beta = d_beta.p; ua.g_eig = d_g_eig.p; ua.g_scale = d_g_scale.p;
         ua.dpow = d_dpow.p; ua.PinvT = d_PinvT.p; ua.Prm = d_Prm.p; ua.Xs = nullptr; ua.Ys = nullptr;
-        ua.pos_gid = d_epos_gid.p; ua.g_span = d_g_span.p;
+        ua.pos_gid = lay.epos_gid.d.p; ua.g_span = d_g_span.p;
         const int nce = n_contigs * Ke;
-        const int LEN = MMi + Mp;                       // per slab: the M x M accumulator and the M diagonal sums
-        d_part_ek.alloc(std::max<size_t>(1, slabs_ek.size()) * LEN);
-        // shares of the cross-slab reduction: ~32 slabs each (un-binned data: thousands of slabs on a handful of (contig, key) pairs)
-        int max_sl = 1;
-        for (int ce = 0; ce < nce; ++ce) max_sl = std::max(max_sl, ek_slab_off[ce + 1] - ek_slab_off[ce]);
-        const int nsh = std::max(1, std::min(128, (max_sl + 31) / 32));
-        d_red_ek.alloc((size_t)nce * nsh * LEN);
+        const int LEN = MMi + Mp, nsh = p.nsh;          // per slab: the M x M accumulator and the M diagonal sums
         const int nblk = ceil_div(ua.nslabs, 4);
         const size_t shm = (size_t)2 * (16 * NT) * (16 * NT + 1) * sizeof(double);
         switch (NT) {
@@ -1006,28 +1030,24 @@ void smcpp_im::launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa) {
             default: F_(4)
 #undef F_
         }
-        sum_parts(d_part_ek.p, d_ek_slab_off.p, d_red_ek.p, LEN, (unsigned)nce, nsh, se);
+        sum_parts(d_part_ek.p, lay.ek_slab_off.d.p, d_red_ek.p, LEN, (unsigned)nce, nsh, se);
         hipLaunchKernelGGL(k_fin_Z2, dim3(nb2, nce), dim3(256), 0, se, fa, (const double *)d_red_ek.p, nsh);
         hipLaunchKernelGGL(k_fin_Y, dim3(nb2, nce), dim3(256), 0, se, fa);
         break;
     }
     case StatsPlan::EIG_CLASSIC:
-        if (!slabs_eg.empty()) {
+        if (!lay.slabs_eg.h.empty()) {
             UWArgs ua;
-            ua.M = M; ua.Mp = Mp; ua.nslabs = (int)slabs_eg.size(); ua.slabs = d_slabs_eg.p; ua.perm = d_perme.p;
+            ua.M = M; ua.Mp = Mp; ua.nslabs = (int)lay.slabs_eg.h.size(); ua.slabs = lay.slabs_eg.d.p; ua.perm = lay.perme.d.p;
             ua.alpha = d_alpha.p; ua.beta = d_beta.p; ua.g_eig = d_g_eig.p; ua.g_scale = d_g_scale.p;
             ua.dpow = d_dpow.p; ua.PinvT = d_PinvT.p; ua.Prm = d_Prm.p; ua.Xs = d_Xs.p; ua.Ys = d_Ys.p; ua.pos_gid = nullptr; ua.g_span = nullptr;
             launch_uw(NT, ua, se);
             // (no reduction pass over the slab partials: k_fin_Z sums the slabs of a bucket itself)
-            launch_rank_acc<1>(acc_args(slabs_eg, d_slabs_eg.p, d_perme.p, nullptr, d_part_e.p, nullptr), false, nullptr, 0, se);
+            launch_rank_acc<1>(acc_args(lay.slabs_eg, lay.perme.d.p, nullptr, d_part_e.p, nullptr), false, nullptr, p.part_e, se);
         }
         if (Ke > 0) {
-            // slices of the groups of one (contig, key): enough blocks to fill the chip when there are many groups
-            int max_b = 0;
-            for (size_t ce = 0; ce + 1 < ce_bucket_off.size(); ++ce) max_b = std::max(max_b, ce_bucket_off[ce + 1] - ce_bucket_off[ce]);
-            const int nsl = std::max(1, std::min(std::min(256, max_b), 2048 / std::max(1, nb2 * n_contigs * Ke)));
-            if (nsl > 1) { d_Zpart.alloc((size_t)nsl * n_contigs * Ke * Mp * Mp); fa.Zpart = d_Zpart.p; }
-            else fa.Zpart = nullptr;
+            const int nsl = p.nsl;
+            fa.Zpart = nsl > 1 ? d_Zpart.p : nullptr;
             hipLaunchKernelGGL(k_fin_Z, dim3(nb2, n_contigs * Ke, nsl), dim3(256), 0, se, fa);
             if (nsl > 1) hipLaunchKernelGGL(k_fin_Zsum, dim3(nb2, n_contigs * Ke), dim3(256), 0, se, fa, nsl, n_contigs * Ke);
             hipLaunchKernelGGL(k_fin_Y, dim3(nb2, n_contigs * Ke), dim3(256), 0, se, fa);
@@ -1040,27 +1060,27 @@ void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
     const hipStream_t sg = plan_stream(p.gamma);
     const int nb2 = ceil_div((long long)Mp * Mp, 256);
     GammaRowArgs ga;
-    ga.M = M; ga.Mp = Mp; ga.nrows = (int)n_e_rows; ga.perm = d_perme.p; ga.row_slab = d_erow_slab.p;
-    ga.slabs = d_slabs_eg.p; ga.g_eig = d_g_eig.p; ga.g_span = d_g_span.p; ga.dun = d_dun.p; ga.dsc = d_dsc.p; ga.dpow = d_dpow.p;
+    ga.M = M; ga.Mp = Mp; ga.nrows = (int)lay.n_e_rows; ga.perm = lay.perme.d.p; ga.row_slab = lay.erow_slab.d.p;
+    ga.slabs = lay.slabs_eg.d.p; ga.g_eig = d_g_eig.p; ga.g_span = d_g_span.p; ga.dun = d_dun.p; ga.dsc = d_dsc.p; ga.dpow = d_dpow.p;
     ga.Prm = d_Prm.p; ga.Pinvrm = d_Pinvrm.p; ga.PinvT = d_PinvT.p; ga.Sq = nullptr;
-    ga.alpha = d_alpha.p; ga.beta = d_beta.p; ga.gamma_rows = d_gamma_rows.p; ga.erow_desc = d_erow_desc.p;
+    ga.alpha = d_alpha.p; ga.beta = d_beta.p; ga.gamma_rows = d_gamma_rows.p; ga.erow_desc = lay.erow_desc.d.p;
     switch (p.gamma_form) {
     case StatsPlan::GAMMA_NONE: break;
     case StatsPlan::GAMMA_PIECES: {
         // long rows at 64 < M <= 256: eigen-power pieces + scan steps (chains_ss.hpp: k_piece_vectors)
         build_gamma_pieces();
         const int MS = 64 * NPL;
-        d_gp_gen.upload(ss_gen, sg);
-        d_gp_cs.alloc((size_t)Ke * 2 * Mp);
-        d_gp_l2d.alloc((size_t)Ke * Mp);
-        const size_t npc = gp_pieces.size();
-        d_gp_pvf.alloc(npc * Mp); d_gp_pvb.alloc(npc * Mp); d_gp_pgam.alloc(npc * Mp);
+        gp.gen.upload(ss_gen, sg);
+        gp.cs.alloc((size_t)Ke * 2 * Mp);
+        gp.l2d.alloc((size_t)Ke * Mp);
+        const size_t npc = gp.pieces.h.size();
+        gp.pvf.alloc(npc * Mp); gp.pvb.alloc(npc * Mp); gp.pgam.alloc(npc * Mp);
         PieceArgs pa;
-        pa.M = M; pa.Mp = Mp; pa.npieces = (int)npc; pa.ntiles = (int)gp_tiles.size();
-        pa.pieces = d_gp_pieces.p; pa.tiles = d_gp_tiles.p; pa.Xs = d_Xs.p; pa.Ys = d_Ys.p; pa.dsc = d_dsc.p;
-        pa.PT = d_PT.p; pa.Pinvrm = d_Pinvrm.p; pa.cs = d_gp_cs.p; pa.l2d = d_gp_l2d.p; pa.pvf = d_gp_pvf.p; pa.pvb = d_gp_pvb.p; pa.pgam = d_gp_pgam.p;
+        pa.M = M; pa.Mp = Mp; pa.npieces = (int)npc; pa.ntiles = (int)gp.tiles.h.size();
+        pa.pieces = gp.pieces.d.p; pa.tiles = gp.tiles.d.p; pa.Xs = d_Xs.p; pa.Ys = d_Ys.p; pa.dsc = d_dsc.p;
+        pa.PT = d_PT.p; pa.Pinvrm = d_Pinvrm.p; pa.cs = gp.cs.p; pa.l2d = gp.l2d.p; pa.pvf = gp.pvf.p; pa.pvb = gp.pvb.p; pa.pgam = gp.pgam.p;
         hipLaunchKernelGGL(k_piece_rowsums, dim3(ceil_div(Ke * 2 * Mp, 256)), dim3(256), 0, sg, Ke, Mp, (const double *)d_PT.p,
-                           (const double *)d_Pinvrm.p, d_gp_cs.p, (const double *)d_dsc.p, d_gp_l2d.p);
+                           (const double *)d_Pinvrm.p, gp.cs.p, (const double *)d_dsc.p, gp.l2d.p);
         if (pa.ntiles > 0) {
             lds_limit_once<k_piece_vectors>();
             const size_t shm = (size_t)4 * 16 * (Mp + 4) * sizeof(double);
@@ -1069,7 +1089,7 @@ void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
         }
         SsArgs sa = SsArgs();
         sa.M = M; sa.Mp = Mp;
-        set_generators(sa, d_gp_gen.p, MS, ss_c0);
+        set_generators(sa, gp.gen.p, MS, ss_c0);
         const int nw = (int)std::min<size_t>(npc, 4096);
         d_gpark.alloc((size_t)nw * 64 * MS);
         const dim3 grid(ceil_div(nw, 4)), block(256);
@@ -1080,14 +1100,14 @@ void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
             default: GP_(4)
 #undef GP_
         }
-        hipLaunchKernelGGL(k_gamma_merge_pieces, dim3((unsigned)ceil_div((long long)n_e_rows * Mp, 256)), dim3(256), 0, sg, Mp, (int)n_e_rows,
-                           (const int *)d_gp_pfirst.p, (const GPiece *)d_gp_pieces.p, (const double *)d_gp_pgam.p, d_gamma_rows.p);
+        hipLaunchKernelGGL(k_gamma_merge_pieces, dim3((unsigned)ceil_div((long long)lay.n_e_rows * Mp, 256)), dim3(256), 0, sg, Mp, (int)lay.n_e_rows,
+                           (const int *)gp.pfirst.d.p, (const GPiece *)gp.pieces.d.p, (const double *)gp.pgam.p, d_gamma_rows.p);
         break;
     }
     case StatsPlan::GAMMA_SCAN: {
         // no eigensystem on this path: 2 span - 1 scan steps per row, one (persistent) wavefront per row, the forward vectors parked
         // as floats in the wavefront's piece of a scratch buffer
-        const int nw = (int)std::min<long long>((long long)n_e_rows, NPL >= 8 ? 1024 : 4096);
+        const int nw = (int)std::min<long long>((long long)lay.n_e_rows, NPL >= 8 ? 1024 : 4096);
         d_gpark.alloc((size_t)nw * ss_max_span * 64 * NPL);
         const dim3 grid(ceil_div(nw, 4)), block(256);
         switch (NPL) {
@@ -1105,7 +1125,7 @@ void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
         const int NW = 4;
         const size_t shm2 = (size_t)((NT <= 2 ? 3 : 2) * Mp * (Mp + 1) + NW * (2 * 16 * (Mp + 1) + Mp * (NT <= 2 ? 17 : 9) + Mp) + Mp) * sizeof(double);
         for (int ce = 0; ce < n_contigs * Ke; ++ce) {
-            const int q0 = ce_row_off[ce], q1 = ce_row_off[ce + 1];
+            const int q0 = lay.ce_row_off[ce], q1 = lay.ce_row_off[ce + 1];
             if (q1 <= q0) continue;
             const int nbatch = std::max(1, std::min(4, (q1 - q0 + 16 * NW * 2048 - 1) / (16 * NW * 2048)));   // batches of 16 rows per wavefront
             const int nblk = ceil_div(q1 - q0, 16 * NW * nbatch);
@@ -1124,14 +1144,16 @@ void smcpp_im::launch_gamma_rows(const StatsPlan &p) {
         hipLaunchKernelGGL(k_span_q, dim3(nb2, G), dim3(256), 0, sg, M, Mp, G, (const int *)d_g_span.p,
                            (const int *)d_g_eig.p, (const double *)d_dsc.p, (const double *)d_dpow.p, d_Sq.p);
         ga.Sq = d_Sq.p;
-        hipLaunchKernelGGL(k_gamma_rows_eig, dim3((unsigned)n_e_rows), dim3(256), (size_t)(3 * Mp + 256) * sizeof(double), sg, ga);
+        hipLaunchKernelGGL(k_gamma_rows_eig, dim3((unsigned)lay.n_e_rows), dim3(256), (size_t)(3 * Mp + 256) * sizeof(double), sg, ga);
         break;
     }
     if (p.gamma_beside) hand_over(EV_GAMMA_DONE, sg, stream);
 }
 
 bool smcpp_im::enqueue_stats(int signal_epoch) {
-    const StatsPlan &p = stats_plan = resolve_stats_plan();
+    // (whether T has generators is the one question with a side effect - ss_gen, a lazy T expanded: asked here, only where the plan depends on it)
+    const StatsPlan &p = stats_plan = resolve_stats_plan(gamma_pieces_fit() && (estep_route.ss_active || ss_generators_only()));
+    size_stats_buffers(p);
     const hipStream_t s = stream, sl = plan_stream(p.loglik);
     if (h_ll_cap < n_contigs) {
         if (h_ll) (void)hipHostFree(h_ll);
@@ -1160,28 +1182,24 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
     LoglikArgs la;
     la.cnorm = d_cnorm.p; la.rowinfo = d_rowinfo.p; la.g_logscale = d_g_logscale.p;
     la.contig_base = d_contig_base.p; la.contig_L = d_contig_L.p; la.partial = d_llpart.p; la.loglik = d_loglik.p;
-    la.logc = d_logc.p; la.nblk = llblk;
+    la.logc = d_logc.p; la.nblk = lay.llblk;
     la.loglik_host = d_ll_view;          // the final kernel writes the per-contig values into the pinned array as well: no copy
     if (p.loglik == StatsPlan::THIRD) fork_from_chains(sl);
-    hipLaunchKernelGGL(k_loglik_partial, dim3(llblk, n_contigs), dim3(256), 0, sl, la);
+    hipLaunchKernelGGL(k_loglik_partial, dim3(lay.llblk, n_contigs), dim3(256), 0, sl, la);
     hipLaunchKernelGGL(k_loglik_final, dim3(n_contigs), dim3(256), 0, sl, la);
     if (p.loglik == StatsPlan::THIRD) HIPCHK(hipEventRecord(ev[EV_LOGLIK_DONE], sl));
     FinArgs fa;
     fa.M = M; fa.Mp = Mp; fa.K = K; fa.G = G; fa.Ke = Ke; fa.n_contigs = n_contigs;
-    fa.eb_slab_off = d_eb_slab_off.p; fa.eb_gid = d_eb_gid.p; fa.ce_bucket_off = d_ce_bucket_off.p;
-    fa.s1_slab_off = d_s1_slab_off.p; fa.gk_slab_off = d_gk_slab_off.p; fa.g_span = d_g_span.p;
+    fa.eb_slab_off = lay.eb_slab_off.d.p; fa.eb_gid = lay.eb_gid.d.p; fa.ce_bucket_off = lay.ce_bucket_off.d.p;
+    fa.s1_slab_off = lay.s1_slab_off.d.p; fa.gk_slab_off = lay.gk_slab_off.d.p; fa.g_span = d_g_span.p;
     fa.e_kid = d_e_kid.p; fa.dsc = d_dsc.p; fa.dun = d_dun.p; fa.Prm = d_Prm.p; fa.Pinvrm = d_Pinvrm.p;
-    fa.E = d_E.p; fa.Td = d_Td.p; fa.ZS = ZS; fa.red_e = nullptr; fa.red_1 = d_red_1.p; fa.red_g = d_red_g.p; fa.ZG = p.s1_one_pass ? ZG : 1;
+    fa.E = d_E.p; fa.Td = d_Td.p; fa.ZS = lay.ZS; fa.red_e = nullptr; fa.red_1 = d_red_1.p; fa.red_g = d_red_g.p; fa.ZG = p.s1_one_pass ? lay.ZG : 1;
     fa.alpha = d_alpha.p; fa.beta = d_beta.p; fa.contig_base = d_contig_base.p;
     fa.Z = d_Z.p; fa.Y = d_Y.p; fa.xisum = d_xisum.p; fa.gsum = d_gsum.p; fa.gamma0 = d_gamma0.p;
     fa.dpow = d_dpow.p;
-    fa.part_e = nullptr;
+    fa.part_e = p.part_e ? d_part_e.p : nullptr;
+    if (p.red_e) fa.red_e = d_red_e.p;
     fa.eigfree = estep_route.eigfree ? 1 : 0;
-    if (!slabs_eg.empty() && p.eigen != StatsPlan::EIG_GEN2) {
-        d_part_e.alloc(std::max<size_t>(1, p.teams_span_gt1 ? teams_eg.size() : slabs_eg.size()) * Mp * Mp);
-        fa.part_e = d_part_e.p;
-        if (estep_route.eigfree) { d_red_e.alloc(std::max<size_t>(1, eb_gid.size()) * Mp * Mp); fa.red_e = d_red_e.p; }
-    }
     // ---- the two branches ----
     if (p.rank_early) {
         launch_span_gt1_rank(p);
@@ -1191,7 +1209,7 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
     launch_span_gt1_branch(p, fa);
     if (p.gsum_at == StatsPlan::GSUM_SPAN_GT1_TAIL) {
         HIPCHK(hipStreamWaitEvent(plan_stream(p.span_gt1), ev[EV_S1_SCALARS], 0));
-        sum_parts(d_gpart.p, d_gk_slab_off.p, d_red_g.p, Mp, n_contigs * K, 1, plan_stream(p.span_gt1));
+        sum_parts(d_gpart.p, lay.gk_slab_off.d.p, d_red_g.p, Mp, n_contigs * K, 1, plan_stream(p.span_gt1));
     }
     // ---- joins: the main stream waits for ONE event of the second stream (every wait is a barrier packet of a few microseconds on
     // the queue it is put on, signalled or not); the third stream joins through the second where that carries the span-1 branch ----
@@ -1221,26 +1239,17 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
 // The pieces of the eigen rows (chains_ss.hpp: k_piece_vectors): at most 64 positions each, in the order of the sorted eigen-row
 // permutation (so the pieces of one (contig, eigen key) are contiguous and a row's pieces are in position order); tiles of sixteen
 // pieces of ONE eigen key that need an interpolated vector (every piece of a row that has more than one).
-long long smcpp_im::gamma_piece_count() {
-    if (gp_count < 0) {
-        gp_count = 0;
-        for (size_t q = 0; q < perme.size(); ++q) gp_count += (groups[slabs_eg[erow_slab[q]].aux].span + 63) / 64;
-    }
-    return gp_count;
-}
-
 void smcpp_im::build_gamma_pieces() {
-    if (gp_built) return;
+    if (gp.built) return;
     constexpr int PL = 64;
-    gp_pieces.clear(); gp_tiles.clear(); gp_pfirst.clear();
-    gp_pfirst.reserve(perme.size() + 1);
+    gp.pfirst.h.reserve(lay.perme.h.size() + 1);
     GTile cur; cur.es = -1; cur.cnt = 0;
-    auto flush = [&]() { if (cur.cnt > 0) { for (int k = cur.cnt; k < 16; ++k) cur.pid[k] = cur.pid[cur.cnt - 1]; gp_tiles.push_back(cur); } cur.cnt = 0; };
-    for (size_t q = 0; q < perme.size(); ++q) {
-        const Slab &sl = slabs_eg[erow_slab[q]];
+    auto flush = [&]() { if (cur.cnt > 0) { for (int k = cur.cnt; k < 16; ++k) cur.pid[k] = cur.pid[cur.cnt - 1]; gp.tiles.h.push_back(cur); } cur.cnt = 0; };
+    for (size_t q = 0; q < lay.perme.h.size(); ++q) {
+        const Slab &sl = lay.slabs_eg.h[lay.erow_slab.h[q]];
         const Group &gr = groups[sl.aux];
-        const long long row = sl.base + perme[q];
-        gp_pfirst.push_back((int)gp_pieces.size());
+        const long long row = sl.base + lay.perme.h[q];
+        gp.pfirst.h.push_back((int)gp.pieces.h.size());
         const int np = (gr.span + PL - 1) / PL;
         for (int j = 0; j < np; ++j) {
             GPiece pc;
@@ -1248,17 +1257,17 @@ void smcpp_im::build_gamma_pieces() {
             if (np > 1) {
                 if (cur.es != gr.eig || cur.cnt == 16) flush();
                 cur.es = gr.eig;
-                cur.pid[cur.cnt++] = (int)gp_pieces.size();
+                cur.pid[cur.cnt++] = (int)gp.pieces.h.size();
             }
-            gp_pieces.push_back(pc);
+            gp.pieces.h.push_back(pc);
         }
     }
     flush();
-    gp_pfirst.push_back((int)gp_pieces.size());
-    d_gp_pieces.upload(gp_pieces, stream);
-    d_gp_tiles.upload(gp_tiles, stream);
-    d_gp_pfirst.upload(gp_pfirst, stream);
-    gp_built = true;
+    gp.pfirst.h.push_back((int)gp.pieces.h.size());
+    gp.pieces.d.upload(gp.pieces.h, stream);
+    gp.tiles.d.upload(gp.tiles.h, stream);
+    gp.pfirst.d.upload(gp.pfirst.h, stream);
+    gp.built = true;
 }
 
 // Event intervals of the last E-step -> timing[] (lazily: see estep)
