@@ -319,6 +319,16 @@ int smcpp_dev_q_emulate(int n, int n_hs, const double *hs, double polarization_e
                         int nder, const double *s, double theta, double rho, double alpha, int K, const int *keys,
                         const double *g0, const double *xi, const double *gs, double *val, double *jac);
 
+/* Test hook (no device needed): the transition matrix T [M x M] of a one-population model (pieces a, s; seeds da [Kp x nder],
+ * nder >= 1; hidden states hs [n_hs], M = n_hs - 1), its dense Jacobian dT [M x M x nder] as the engine expands it from the O(M)
+ * generator planes, and the four COEFFICIENT PLANES [nder x M] the vector form of the score track (SMCPP_SCORE_FORM=vectors)
+ * contracts with instead of dT.  With c0 = 1e-5 / (M + 1), entry by entry
+ *     dT_d(i, j) = cL_d(j) T(i, j)  (i > j),   (cP_d(i) + cW_d(j)) (T(i, j) - c0)  (i < j),   cD_d(j) T(j, j)  (i == j),
+ * except above the diagonal where the raw entry lies below the 1e-20 floor (dT is zero there, the planes keep the raw product).
+ * Fails when the generators need the pairwise fallback (cumulative hazard beyond 575). */
+int smcpp_host_score_planes(int Kp, const double *a, const double *da, int nder, const double *s, int n_hs, const double *hs,
+                            double rho, double *T, double *dT, double *cD, double *cL, double *cW, double *cP);
+
 /* PyRateFunction.R / average_coal_times (smcpp/_smcpp.pyx:370-389): cumulative hazard R at t[0..nt) for the model
  * pieces (a, s) and, when n_hs >= 2, E[T | hs_i <= T < hs_{i+1}] for the n_hs-1 intervals. */
 int smcpp_host_rate_function(int Kp, const double *a, const double *s, int n_hs, const double *hs, int nt,
@@ -535,11 +545,23 @@ int smcpp_loglik_windows(smcpp_im *im, int contig, long long window_bp, long lon
  * (SMCPP_SCORE_WAVES), the call order or what ran before; the posterior buffers, the statistics and the loglik track are neither
  * needed beyond the stored vectors nor disturbed.  The Jacobian of a device-prepared emission table is copied out without
  * replacing the host's table, so a later smcpp_q KEEPS its device route after a score call ("q_route" stays what it was).
- * smcpp_describe reports "score_items" (engine rows walked), "score_waves" and "score_park" ("lds": where a block's vectors wait).
+ * smcpp_describe reports "score_items" (engine rows walked), "score_waves", "score_park" ("lds" / "global": where a block's vectors
+ * wait) and "score_form" ("matrix" / "vectors": the form of the last score call).
+ * The row walk has two forms, chosen by the switch SMCPP_SCORE_FORM, which is read at EVERY call (one manager answers in both
+ * without a new E-step):
+ *     matrix  (unset)  one column of the M x M accumulator sum_p x_{p-1}(i) w_p(j) / Z_p per lane, contracted with the dense dT once
+ *                      per row (score_track_dev.hpp); one state per lane, M <= 64.
+ *     vectors          four O(M) accumulators per row against the coefficient planes of the transition Jacobian
+ *                      (score_vec_dev.hpp; the dense dT is not expanded); one to four states per lane, M <= 256.  It needs the
+ *                      generator planes of the transition Jacobian, which one-population models prepared on the device have: it
+ *                      refuses SMCPP_PREP=host, two-population managers and a transition matrix that took the pairwise fallback.
+ *                      Above the diagonal an entry below the 1e-20 floor keeps its raw derivative where the dense Jacobian has
+ *                      zero: less than 1e-20 / c0 |dT / T| per position, c0 = 1e-5 / (M + 1).
  * Each call fails before anything is launched, and leaves the manager usable, when no E-step has run, the last one ran without
  * save_gamma, the contig index is out of range, the parameters were set again since the last E-step, they carry no derivative
  * seeds (nder = 0, or smcpp_set_raw), the transition matrix lacks the semiseparable structure, there are more than 64 hidden states
- * (the kernel keeps one column of the M x M accumulator per lane), the selection is bad (start < 0, stop > L + 1, start >= stop,
+ * (the matrix form keeps one column of the M x M accumulator per lane) or more than 256 (the vectors
+ * form), SMCPP_SCORE_FORM holds another word, the selection is bad (start < 0, stop > L + 1, start >= stop,
  * step < 1) or window_bp < 1, an output would exceed 2^31 - 1 elements or the scratch 1 GiB.
  *
  * smcpp_score_rows: the column selection range(start, stop, step) over 0 .. L, the selection rule of smcpp_posterior_summary.

@@ -218,6 +218,20 @@ def dev_q_emulate(n, hs, polarization_error, a, da, s, theta, rho, alpha, keys, 
     return val, jac
 
 
+def host_score_planes(a, da, s, hs, rho):
+    """T [M, M], its dense Jacobian dT [M, M, nder] and the coefficient planes cD, cL, cW, cP [nder, M] of the score track's vector
+    form for a one-population model with seeds ``da`` [K, nder] (include/smcpp_engine.h: smcpp_host_score_planes)."""
+    a = np.ascontiguousarray(a, dtype=np.float64); s = np.ascontiguousarray(s, dtype=np.float64)
+    da = np.ascontiguousarray(da, dtype=np.float64).reshape(len(a), -1)
+    hs = np.ascontiguousarray(hs, dtype=np.float64)
+    M, nder = len(hs) - 1, da.shape[1]
+    out = dict(T=np.zeros((M, M)), dT=np.zeros((M, M, nder)), cD=np.zeros((nder, M)), cL=np.zeros((nder, M)), cW=np.zeros((nder, M)),
+               cP=np.zeros((nder, M)))
+    check(lib().smcpp_host_score_planes(len(a), dptr(a), dptr(da), nder, dptr(s), len(hs), dptr(hs), float(rho), dptr(out["T"]),
+                                        dptr(out["dT"]), dptr(out["cD"]), dptr(out["cL"]), dptr(out["cW"]), dptr(out["cP"])))
+    return out
+
+
 def host_rate_function(a, s, t, hs=None):
     """R(t) (and average coalescence times per hidden-state interval when ``hs`` is given)."""
     a = np.ascontiguousarray(a, dtype=np.float64)

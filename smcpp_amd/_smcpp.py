@@ -343,7 +343,8 @@ class _PyInferenceManager:
         last `save_gamma` E-step, for the `nder` derivative seeds of the parameters it ran on (a differentiable model); column 0
         holds the initial distribution's share.  `parts=True`: `[3, nder, ncols]`, the initial, emission and transition part; the
         last two sum over all columns and contigs to rows 1 + 2 and 3 of `Q_with_gradient()`'s Jacobian (row 0 weighs the initial
-        part by the stored, unnormalised mass of column 0).  At most 64 hidden states.
+        part by the stored, unnormalised mass of column 0).  At most 64 hidden states; at most 256 with SMCPP_SCORE_FORM=vectors
+        (`_engine.set_option`; read at every call; one-population models).
         (include/smcpp_engine.h: smcpp_score_rows.)"""
         start, stop, step, ncols = self._selection(c, start, stop, step)
         parts = 1 if parts else 0

@@ -103,6 +103,7 @@ cdef extern from "smcpp_engine.h":
     int smcpp_host_prep_onepop_jac(int n, int n_hs, const double *hs, double polarization_error, int Kp, const double *a, const double *da, int nder, const double *s, double theta, double rho, double alpha, int K, const int *keys, double *pi, double *T, double *E, double *dpi, double *dT, double *dE) nogil
     int smcpp_dev_prep_onepop(int n, int n_hs, const double *hs, double polarization_error, int Kp, const double *a, const double *da, int nder, const double *s, double theta, double rho, double alpha, int K, const int *keys, int mode, double *pi, double *T, double *E, double *dpi, double *dT, double *dE, double *sfs, double *dsfs) nogil
     int smcpp_dev_q_emulate(int n, int n_hs, const double *hs, double polarization_error, int Kp, const double *a, const double *da, int nder, const double *s, double theta, double rho, double alpha, int K, const int *keys, const double *g0, const double *xi, const double *gs, double *val, double *jac) nogil
+    int smcpp_host_score_planes(int Kp, const double *a, const double *da, int nder, const double *s, int n_hs, const double *hs, double rho, double *T, double *dT, double *cD, double *cL, double *cW, double *cP) nogil
     int smcpp_host_rate_function(int Kp, const double *a, const double *s, int n_hs, const double *hs, int nt, const double *t, double *R_out, double *avg_ct_out) nogil
     int smcpp_host_rate_function_jac(int Kp, const double *a, const double *da, int nder, const double *s, int n_hs, const double *hs, int nt, const double *t, double *R_out, double *dR_out, double *avg_ct_out, double *davg_ct_out) nogil
     int smcpp_host_random_coal_times(int Kp, const double *a, const double *s, double t1, double t2, int K, const unsigned long long *seeds, double *t_out, double *R_out) nogil

@@ -41,6 +41,7 @@
 #include "posterior_dev.hpp"    // products of the per-row posteriors: columns, per-column summaries, windows
 #include "posterior_trans_dev.hpp"   // posterior transition products: stay / up / down per row and per window
 #include "score_track_dev.hpp"       // score track: d loglik / d direction per row (initial, emission, transition part) and per window
+#include "score_vec_dev.hpp"         // ... its vector form: four O(M) accumulators per row instead of the M x M one, M <= 256
 #include "posterior_paths_dev.hpp"   // posterior paths: forward filtering, backward sampling (state / up / down per row, per position)
 #include "posterior_pos_dev.hpp"     // posterior positions: the marginal of single positions on a grid, its summaries, exact windows
 #include "loglik_track_dev.hpp"      // log-likelihood track: log c per caller's row, l(p) on a grid of positions, per window

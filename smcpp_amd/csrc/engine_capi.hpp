@@ -626,7 +626,7 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         s += t;
         // ... and of the last score track call: the engine rows it walked, its wavefronts and where a block's vectors are parked
         s += ", \"score_items\": " + std::to_string(im->sc_items) + ", \"score_waves\": " + std::to_string(im->sc_waves);
-        s += ", \"score_park\": \"lds\"";
+        s += std::string(", \"score_park\": \"") + (im->sc_vectors ? "global" : "lds") + "\", \"score_form\": \"" + (im->sc_vectors ? "vectors" : "matrix") + "\"";
     }
     s += "}";
     if (buf && cap > 0) {

@@ -263,6 +263,32 @@ int smcpp_dev_q_emulate(int n, int n_hs, const double *hs, double polarization_e
     API_END
 }
 
+// Test hook: the transition matrix of a one-population model with derivative seeds, its dense Jacobian as the engine expands it
+// (transition_expand_jac) and the four coefficient planes the vector form of the score track contracts with instead (score_planes).
+int smcpp_host_score_planes(int Kp, const double *a, const double *da, int nder, const double *s, int n_hs, const double *hs,
+                            double rho, double *T, double *dT, double *cD, double *cL, double *cW, double *cP) {
+    API_BEGIN
+    if (!da || nder < 1) throw std::runtime_error("score planes: no derivative seeds");
+    if (n_hs < 2) throw std::runtime_error("score planes: fewer than two hidden-state boundaries");
+    const std::vector<double> hsv(hs, hs + n_hs);
+    const int M = n_hs - 1;
+    smcpp_host::DualScope sc(nder);
+    const auto p = dual_model(Kp, a, da, nder, s);
+    smcpp_host::RateFunctionT<smcpp_host::dual> eta(p, hsv);
+    const std::vector<smcpp_host::dual> act = eta.average_coal_times();
+    std::vector<double> Tv, dTv, diag(M), pl[4];
+    smcpp_host::TransitionGenJac tj;
+    if (!host_transition_with_planes(eta, act, rho, nder, Tv, tj)) throw std::runtime_error("score planes: the transition generators need the pairwise fallback");
+    smcpp_host::transition_expand_jac(tj, dTv);
+    for (int j = 0; j < M; ++j) diag[j] = Tv[(size_t)j * M + j];
+    score_planes(tj, diag.data(), pl[0], pl[1], pl[2], pl[3]);
+    std::memcpy(T, Tv.data(), sizeof(double) * Tv.size());
+    std::memcpy(dT, dTv.data(), sizeof(double) * dTv.size());
+    double *dst[4] = {cD, cL, cW, cP};
+    for (int q = 0; q < 4; ++q) std::memcpy(dst[q], pl[q].data(), sizeof(double) * pl[q].size());
+    API_END
+}
+
 int smcpp_host_random_coal_times(int Kp, const double *a, const double *s, double t1, double t2, int K,
                                  const unsigned long long *seeds, double *t_out, double *R_out) {
     API_BEGIN

@@ -389,7 +389,17 @@ struct smcpp_im {
     int score_check(int c);                       // throws unless a score call can run on contig c; -> checkpoint vectors per wavefront
     void score_tables();                          // -> d_sc_tab (keeps E_on_dev: a later smcpp_q stays on its device route)
     const double *score_rows(int c, long long start, long long step, long long ncols, int parts, int nck);   // -> device, on `stream`
-    bool ss_generators_only();             // the generators of T into ss_gen / ss_c0 (no underflow bound: the walks rescale every step)
+    // ... in its VECTOR form (score_vec_dev.hpp; SMCPP_SCORE_FORM=vectors, read at every call): G_pi | the four coefficient planes of
+    // the transition Jacobian | G_E, each 64 NPL wide, from the generator planes `tgen` - the dense dT is not expanded
+    DevBuf<double> d_sv_tab;
+    DevBuf<float> d_sv_park;
+    bool sv_tab_valid = false;                    // d_sv_tab belongs to the last E-step (cleared where sc_tab_valid is)
+    bool sc_vectors = false;                      // the form of the last score call (smcpp_describe)
+    bool score_form_vectors() const;              // what SMCPP_SCORE_FORM asks for now (throws on a value it does not know)
+    void score_tables_vec();                      // -> d_sv_tab (keeps E_on_dev as score_tables does)
+    void score_rows_vec(int c, int nck);          // k_score_rows_vec -> d_sc_eng, on `stream`
+    void score_rows_matrix(int c, int nck);       // k_score_rows -> d_sc_eng, on `stream`
+    bool ss_generators_only();            // the generators of T into ss_gen / ss_c0 (no underflow bound: the walks rescale every step)
     DevBuf<float> d_gpark;                 // k_gamma_rows_scan: [wavefronts][max span][64 NPL] parked forward vectors
     SsArgs ss_args;
     std::vector<Chunk> chunks_b;           // backward chunks of the scan chains (more and shorter than the forward ones)

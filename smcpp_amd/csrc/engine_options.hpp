@@ -11,7 +11,7 @@ enum OptId {
     O_COOP_BPC, O_ROWS_PER_CHUNK, O_SS_WPC, O_SS_HALO, O_HALO_LF, O_HALO_DF, O_HALO_LB, O_HALO_DB, O_SS_FWD_SHARE, O_STATS_TEAM,
     O_SLAB_ROWS, O_POWER_PREPASS, O_PREP, O_Q, O_EIG_TEAM, O_EIG_PIN, O_BWD_PRIO, O_COOP_TAB, O_POWER_DEBUG, O_BWD_PRIO_MASK,
     O_DEBUG_CYCLES, O_SS_H32, O_SS_MIXED, O_SS_LIGHT_F, O_SS_LIGHT_B, O_SS_CERT_PASS, O_POLL, O_GAMMA_SIDE,
-    O_SPAN_SCAN, O_S1_FUSE, O_EIGFREE, O_CSFS_DIRECT, O_RANK_WIDE, O_GAMMA_SCAN, O_GAMMA_PIECES, O_SPLIT_SPANS, O_T_LAZY, O_DEBUG_POISON, O_DEBUG_POISON_ONLY, O_DEBUG_POISON_LOG, O_PATH_BATCH, O_LL_WAVES, O_SS_JUMP, O_SCORE_WAVES, O_COUNT
+    O_SPAN_SCAN, O_S1_FUSE, O_EIGFREE, O_CSFS_DIRECT, O_RANK_WIDE, O_GAMMA_SCAN, O_GAMMA_PIECES, O_SPLIT_SPANS, O_T_LAZY, O_DEBUG_POISON, O_DEBUG_POISON_ONLY, O_DEBUG_POISON_LOG, O_PATH_BATCH, O_LL_WAVES, O_SS_JUMP, O_SCORE_WAVES, O_SCORE_FORM, O_COUNT
 };
 
 struct OptDef { const char *name, *help; };
@@ -75,6 +75,9 @@ static const OptDef OPT_DEFS[O_COUNT] = {
     {"SMCPP_LL_WAVES",       "cap on the wavefronts of the log-likelihood track's row walk (default: one per walked row up to 4096, 1024 from 8 states per lane). The values do not depend on it (test switch)"},
     {"SMCPP_SS_JUMP",        "0: no power jumps in the rows of the dominant key (scan chains, M <= 64); 16, 8 or 4: that power of the key's operator, on inputs of any size (unset: 8, from 200 000 positions on)"},
     {"SMCPP_SCORE_WAVES",    "cap on the wavefronts of the score track's row walk (default: one per engine row up to 1024). The values do not depend on it (test switch)"},
+    {"SMCPP_SCORE_FORM",     "matrix | vectors: the form of the score track's row walk, read at every score call (unset: matrix - one column of the M x M "
+                             "accumulator per lane, M <= 64). vectors: four O(M) accumulators against the coefficient planes of the transition "
+                             "Jacobian, M <= 256, one-population models prepared on the device"},
 };
 // clang-format on
 

@@ -215,6 +215,45 @@ void smcpp_im::ensure_dT() {
     dT_valid = true;
 }
 
+// The Jacobian of T as O(M) COEFFICIENT PLANES [nder][M] each, from the generator planes (the vector form of the score track,
+// score_vec_dev.hpp): with T as transition_expand forms it and `diag` [M] its diagonal,
+//     dT_d(i, j) = cL_d(j) T(i, j)                        below the diagonal (the entry depends on the column only),
+//                = (cP_d(i) + cW_d(j)) (T(i, j) - c0)     above it (rank two: dpf_i W_j + pf_i dW_j),
+//                = cD_d(j) T(j, j)                        on it (the diagonal closes the row over the UNfloored entries).
+// The row sum's derivative comes from prefix sums of ded and suffix sums of W, dW, as ss_generators_from_tgen takes the value.  cL
+// and cD are zero where the raw entry is below transition_expand's 1e-20 floor (a floored entry has a zero Jacobian); above the
+// diagonal the floor is per entry and NOT representable here: a floored entry keeps raw (cP + cW) where transition_expand_jac has
+// zero, raw < 1e-20 beside T >= c0 ("Score track", has the bound).
+static void score_planes(const smcpp_host::TransitionGenJac &tj, const double *diag, std::vector<double> &cD, std::vector<double> &cL,
+                         std::vector<double> &cW, std::vector<double> &cP) {
+    const int M = tj.M, nder = tj.nder;
+    const double beta = 1e-5, c0 = beta / (double)(M + 1), om = 1.0 - beta;
+    const size_t n = (size_t)M * nder;
+    cD.assign(n, 0.0); cL.assign(n, 0.0); cW.assign(n, 0.0); cP.assign(n, 0.0);
+    std::vector<double> below(M, 0.0), above(M + 1, 0.0), dbelow(n, 0.0), dabove(n + nder, 0.0);
+    for (int j = 1; j < M; ++j) {
+        below[j] = below[j - 1] + tj.ed[j - 1];
+        for (int d = 0; d < nder; ++d) dbelow[(size_t)j * nder + d] = dbelow[(size_t)(j - 1) * nder + d] + tj.ded[(size_t)(j - 1) * nder + d];
+    }
+    for (int c = M - 1; c >= 1; --c) {
+        above[c] = above[c + 1] + tj.W[c];                                         // sum_{k >= c} W[k]
+        for (int d = 0; d < nder; ++d) dabove[(size_t)c * nder + d] = dabove[(size_t)(c + 1) * nder + d] + tj.dW[(size_t)c * nder + d];
+    }
+    for (int j = 0; j < M; ++j) {
+        const bool dfloor = 1.0 - (below[j] + tj.pf[j] * above[j + 1]) < 1e-20;
+        const bool lfloor = j + 1 >= M || tj.ed[j] < 1e-20;
+        const double g = lfloor ? 1.0 : tj.ed[j] * om + c0;                        // T(i, j), i > j
+        for (int d = 0; d < nder; ++d) {
+            const size_t o = (size_t)d * M + j, p = (size_t)j * nder + d;
+            const double dsum = dbelow[p] + (tj.dpf[p] * above[j + 1] + tj.pf[j] * dabove[(size_t)(j + 1) * nder + d]);
+            cD[o] = dfloor ? 0.0 : -dsum * om / diag[j];
+            cL[o] = lfloor ? 0.0 : tj.ded[p] * om / g;
+            cW[o] = j >= 1 && tj.W[j] > 0.0 ? tj.dW[p] / tj.W[j] : 0.0;
+            cP[o] = tj.pf[j] > 0.0 ? tj.dpf[p] / tj.pf[j] : 0.0;
+        }
+    }
+}
+
 // HMM::Q (src/hmm.cpp:155-193) summed over contigs (inference_manager.cpp:116-126) and its forward-mode gradient, evaluated on
 // the device from the statistics that already live there, the device-prepared emission table (+ planes) and the generators of
 // the transition matrix.  Returns false when this call has to take the host route (no device preparation, a local / global

@@ -1396,7 +1396,7 @@ void smcpp_im::estep() {
     gamma_valid = save_gamma;
     estep_done = true;
     dirty = false;
-    sc_tab_valid = false;            // (the score track's tables belong to the parameters of the E-step before)
+    sc_tab_valid = sv_tab_valid = false;   // (the score track's tables belong to the parameters of the E-step before)
 }
 
 void smcpp_im::fetch_stats() {

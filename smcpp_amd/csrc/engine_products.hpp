@@ -959,12 +959,31 @@ int smcpp_im::score_check(int c) {
     if (nder < 1)
         throw std::runtime_error("score track: the parameters carry no derivative seeds (nder = 0): set them with seeds and run the "
                                  "E-step again");
-    if (M > 64 || NPL != 1)
+    const bool vec = score_form_vectors();
+    // (the matrix form's refusal keeps its text to the letter - tests/test_gpu_product_refusals.py holds it; SMCPP_SCORE_FORM=vectors,
+    // the way past 64 states, is named in the header, the README and the switch table)
+    if (!vec && (M > 64 || NPL != 1))
         throw std::runtime_error("score track: more than 64 hidden states (" + std::to_string(M) + "): the kernel keeps one column of the "
                                  "M x M accumulator per lane and exists at one state per lane only");
+    if (vec) {
+        const std::string who = "score track (SMCPP_SCORE_FORM=vectors): ";
+        if (NPL > 4)
+            throw std::runtime_error(who + "more than 256 hidden states (" + std::to_string(M) + "): the kernel exists at one to four "
+                                     "states per lane; use fewer hidden states");
+        HIPCHK(hipSetDevice(device));
+        prepare_params();                              // (fresh since the E-step: !dirty)
+        if (!tgen_valid || !tgen.ok || tgen.M != M || tgen.nder != nder)
+            throw std::runtime_error(who + "the generator planes of the transition Jacobian do not exist for the last E-step's parameters "
+                                     "(a model prepared on the host - SMCPP_PREP=host -, a two-population manager, or a transition matrix "
+                                     "that needed the pairwise fallback): " +
+                                     (M <= 64 ? "unset SMCPP_SCORE_FORM, the matrix form serves this manager"
+                                              : "prepare a one-population model on the device (unset SMCPP_PREP) and run the E-step again"));
+    }
     const int smax = longest_row(c), nck = walk_checkpoints(smax, SC_BLK);
-    // scratch: the three parts of every direction per engine row + one wavefront's checkpoints at the least
-    const size_t bytes = ((size_t)3 * nder * ((size_t)Ls[c] + 1) + (size_t)nck * 64) * sizeof(double);
+    // scratch: the three parts of every direction per engine row + one wavefront's checkpoints (and parked block) at the least
+    const size_t MS = (size_t)64 * NPL;
+    const size_t bytes = ((size_t)3 * nder * ((size_t)Ls[c] + 1) + (size_t)nck * MS) * sizeof(double) +
+                         (vec ? (size_t)SV_BLK * 4 * MS * sizeof(float) : 0);
     if (bytes > (1ull << 30))
         throw std::runtime_error("score track: the scratch (" + std::to_string(nder) + " directions x 3 parts x " + std::to_string(Ls[c] + 1) +
                                  " engine rows, the checkpoints of a row of " + std::to_string(smax) + " positions) exceeds the cap of 1 GiB");
@@ -975,6 +994,12 @@ static void score_cap(long long per_col, long long ncols, const char *what) {
     if (ncols > ((1LL << 31) - 1) / std::max<long long>(1, per_col))
         throw std::runtime_error(std::string("score track: ") + what + " (" + std::to_string(per_col) + " x " + std::to_string(ncols) +
                                  ") exceed the cap of 2^31 - 1 elements per call: ask for a narrower selection or a wider window");
+}
+
+bool smcpp_im::score_form_vectors() const {
+    if (!opt().has(smcpp_opt::O_SCORE_FORM) || opt().is(smcpp_opt::O_SCORE_FORM, "matrix")) return false;
+    if (opt().is(smcpp_opt::O_SCORE_FORM, "vectors")) return true;
+    throw std::runtime_error("score track: SMCPP_SCORE_FORM is 'matrix' or 'vectors', not '" + opt().str(smcpp_opt::O_SCORE_FORM) + "'");
 }
 
 // G_pi [nder][64] | dT [nder][64][64] | G_E [K][nder][64] from the host arrays the Jacobian getters copy out, zero beyond M and
@@ -1010,13 +1035,93 @@ void smcpp_im::score_tables() {
     sc_tab_valid = true;
 }
 
+// The vector form's tables, MS = 64 NPL wide: G_pi [nder][MS] | cD, cL, cW, cP / d [nder][4][MS] | G_E [K][nder][MS], the last two by
+// BACKWARD position (state j at MS - 1 - j, as ss_pack_generators mirrors the backward generators), zero beyond M and where a value
+// is not positive.  The transition planes come from the generator planes (score_planes): the dense dT is not expanded.  d is the
+// diagonal the walk's generators hold, so that the parked stay addend d_i x(i) times cP(i) / d_i is x(i) cP(i).
+void smcpp_im::score_tables_vec() {
+    if (sv_tab_valid) return;
+    HIPCHK(hipSetDevice(device));
+    std::vector<double> Eloc, dEloc;
+    const std::vector<double> *Ev = &E, *dEv = &dE;
+    if (E_on_dev) {
+        fetch_prepared_table(Eloc, dEloc, false);
+        Ev = &Eloc; dEv = &dEloc;
+    }
+    const size_t nd = (size_t)nder, MS = (size_t)64 * NPL;
+    if (dpi.size() != (size_t)M * nd || Ev->size() != (size_t)K * M || dEv->size() != (size_t)K * M * nd)
+        throw std::runtime_error("score track: the Jacobians of pi and E are not available for the last E-step's parameters");
+    const double *diag = &ss_gen[5 * MS];              // f_d (post_transitions_check has seen the generators)
+    std::vector<double> pl[4];
+    score_planes(tgen, diag, pl[0], pl[1], pl[2], pl[3]);
+    std::vector<double> tab(nd * MS + nd * 4 * MS + (size_t)K * nd * MS, 0.0);
+    double *gp = tab.data(), *gt = gp + nd * MS, *ge = gt + nd * 4 * MS;
+    for (int d = 0; d < nder; ++d)
+        for (int i = 0; i < M; ++i) {
+            const size_t p = MS - 1 - i;
+            gp[d * MS + i] = pi[i] > 0.0 ? dpi[(size_t)i * nd + d] / pi[i] : 0.0;
+            for (int q = 0; q < 4; ++q) gt[((size_t)d * 4 + q) * MS + p] = pl[q][(size_t)d * M + i] / (q == 3 ? diag[i] : 1.0);
+            for (int k = 0; k < K; ++k) {
+                const double e = (*Ev)[(size_t)k * M + i];
+                ge[((size_t)k * nd + d) * MS + p] = e > 0.0 ? (*dEv)[((size_t)k * M + i) * nd + d] / e : 0.0;
+            }
+        }
+    d_sv_tab.upload(tab, stream);
+    HIPCHK(hipStreamSynchronize(stream));              // (`tab` is a local: the copy has to be done before it goes)
+    sv_tab_valid = true;
+}
+
+// k_score_rows_vec over the engine rows of contig c -> d_sc_eng.  Scratch as post_transitions sizes it: one persistent wavefront per
+// engine row up to walk_slots(), fewer where the parked blocks and checkpoints would pass 1 GiB with the parts, or SMCPP_SCORE_WAVES says so.
+void smcpp_im::score_rows_vec(int c, int nck) {
+    score_tables_vec();
+    const int Le = Ls[c];
+    const size_t nd = (size_t)nder, MS = (size_t)64 * NPL;
+    const SsArgs sa = walk_generators();
+    SvArgs a = SvArgs();
+    a.M = M; a.Mp = Mp; a.L = Le; a.nck = nck; a.nder = nder; a.base = contig_base[c];
+    const size_t left = (1ull << 30) - (size_t)3 * nd * ((size_t)Le + 1) * sizeof(double);         // (score_check: one wavefront fits)
+    const size_t per_wave = (size_t)SV_BLK * 4 * MS * sizeof(float) + (size_t)nck * MS * sizeof(double);
+    long long nw = walk_waves(Le, walk_slots(), per_wave, left);
+    if (opt().has(smcpp_opt::O_SCORE_WAVES)) nw = std::min(nw, std::max<long long>(1, opt().ll(smcpp_opt::O_SCORE_WAVES, 1)));
+    d_sv_park.alloc((size_t)nw * SV_BLK * 4 * MS);
+    d_sc_ckpt.alloc(std::max<size_t>(1, (size_t)nw * nck * MS));
+    a.rowinfo = d_rowinfo.p; a.g_span = d_g_span.p; a.E = d_E.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
+    a.gamma0 = d_gamma0.p + (size_t)c * Mp;
+    a.Gpi = d_sv_tab.p; a.planes = a.Gpi + nd * MS; a.GE = a.planes + nd * 4 * MS;
+    a.park = d_sv_park.p; a.ckpt = d_sc_ckpt.p; a.out = d_sc_eng.p;
+    sc_waves = (int)nw; sc_items = Le;
+    const dim3 grid((unsigned)ceil_div(nw, 4)), block(256);
+    for_npl(NPL, [&](auto x) {
+        constexpr int npl = decltype(x)::value;
+        if constexpr (npl <= 4) hipLaunchKernelGGL((k_score_rows_vec<npl>), grid, block, 0, stream, sa, a, (int)nw);   // (score_check: NPL <= 4)
+    });
+    HIPCHK(hipGetLastError());
+}
+
 // The parts (parts != 0: [3][nder][ncols]) or the total ([nder][ncols]) of caller's rows start, start + step, .. of contig c, on the
-// device, on `stream`.  The arguments have been checked (score_check -> nck, the caps).
+// device, on `stream`, in the form SMCPP_SCORE_FORM names at this call.  The arguments have been checked (score_check -> nck, the caps).
 const double *smcpp_im::score_rows(int c, long long start, long long step, long long ncols, int parts, int nck) {
     HIPCHK(hipSetDevice(device));
-    score_tables();
     const int Le = Ls[c];
     const int *first = piece_first_dev(c);
+    d_sc_eng.alloc((size_t)3 * nder * ((size_t)Le + 1));
+    sc_vectors = score_form_vectors();
+    if (sc_vectors) score_rows_vec(c, nck);
+    else score_rows_matrix(c, nck);
+    PostSel sel;
+    sel.start = start; sel.step = step; sel.ncols = ncols;
+    d_sc_sel.alloc((size_t)(parts ? 3 : 1) * nder * ncols);
+    hipLaunchKernelGGL(k_score_select, dim3((unsigned)ceil_div(ncols * nder, 256)), dim3(256), 0, stream, sel, (long long)Le, nder, parts,
+                       first, (const double *)d_sc_eng.p, d_sc_sel.p);
+    HIPCHK(hipGetLastError());
+    return d_sc_sel.p;
+}
+
+// k_score_rows (the matrix form, one state per lane: score_check) over the engine rows of contig c -> d_sc_eng.
+void smcpp_im::score_rows_matrix(int c, int nck) {
+    score_tables();
+    const int Le = Ls[c];
     const SsArgs sa = walk_generators();               // (one state per lane: score_check)
     ScArgs a = ScArgs();
     a.M = M; a.Mp = Mp; a.L = Le; a.nck = nck; a.nder = nder; a.base = contig_base[c];
@@ -1026,7 +1131,6 @@ const double *smcpp_im::score_rows(int c, long long start, long long step, long 
     long long nw = walk_waves(Le, 1024, (size_t)nck * 64 * sizeof(double), left);   // (a contig without rows: wavefront 0 writes column 0)
     if (opt().has(smcpp_opt::O_SCORE_WAVES)) nw = std::min(nw, std::max<long long>(1, opt().ll(smcpp_opt::O_SCORE_WAVES, 1)));
     d_sc_ckpt.alloc(std::max<size_t>(1, (size_t)nw * nck * 64));
-    d_sc_eng.alloc((size_t)3 * nder * ((size_t)Le + 1));
     a.rowinfo = d_rowinfo.p; a.g_span = d_g_span.p; a.E = d_E.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
     a.gamma0 = d_gamma0.p + (size_t)c * Mp;
     a.Gpi = d_sc_tab.p; a.dT = a.Gpi + (size_t)nder * 64; a.GE = a.dT + (size_t)nder * 64 * 64;
@@ -1035,13 +1139,6 @@ const double *smcpp_im::score_rows(int c, long long start, long long step, long 
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_score_rows), hipFuncAttributeMaxDynamicSharedMemorySize, SC_LDS_BYTES));
     hipLaunchKernelGGL(k_score_rows, dim3((unsigned)ceil_div(nw, 4)), dim3(256), SC_LDS_BYTES, stream, sa, a, (int)nw);
     HIPCHK(hipGetLastError());
-    PostSel sel;
-    sel.start = start; sel.step = step; sel.ncols = ncols;
-    d_sc_sel.alloc((size_t)(parts ? 3 : 1) * nder * ncols);
-    hipLaunchKernelGGL(k_score_select, dim3((unsigned)ceil_div(ncols * nder, 256)), dim3(256), 0, stream, sel, (long long)Le, nder, parts,
-                       first, (const double *)d_sc_eng.p, d_sc_sel.p);
-    HIPCHK(hipGetLastError());
-    return d_sc_sel.p;
 }
 
 int smcpp_score_rows(smcpp_im *im, int c, long long start, long long stop, long long step, int parts, double *out) {

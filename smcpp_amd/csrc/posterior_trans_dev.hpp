@@ -50,9 +50,10 @@ struct PtArgs {
 
 constexpr int PT_BLK = 64;
 
-// The three addends of T^T x, state by state (ss_fwd_step's scans, chains_ss.hpp), handed to `sink(k, stay, down, up)`; S = sum x.
+// The addends of T^T x, state by state (ss_fwd_step's scans, chains_ss.hpp), handed to `sink(k, stay, down, low, Z)`; S = sum x.  The
+// addend from below is c0 low + Z: low = sum_{i<j} x_i meets the uniform mix, Z the Phi' part of the upper triangle.
 template <int NPL, typename Sink>
-__device__ __forceinline__ void pt_fwd_addends(const SsFwdC<NPL> &c, double c0, const double (&x)[NPL], double &S, Sink sink) {
+__device__ __forceinline__ void pt_fwd_parts(const SsFwdC<NPL> &c, const double (&x)[NPL], double &S, Sink sink) {
     double lp[NPL], w[NPL];
     lp[0] = x[0];
     w[0] = c.b[0] * x[0];
@@ -79,8 +80,13 @@ __device__ __forceinline__ void pt_fwd_addends(const SsFwdC<NPL> &c, double c0, 
     for (int k = 0; k < NPL; ++k) {
         const double incl = lex + lp[k];                                   // sum_{i <= j} x_i
         const double Z = (k == 0) ? LIp : __builtin_fma(c.cumA[k - 1 < 0 ? 0 : k - 1], LIp, w[k - 1 < 0 ? 0 : k - 1]);
-        sink(k, c.d[k] * x[k], c.g[k] * (S - incl), __builtin_fma(c0, incl - x[k], Z));
+        sink(k, c.d[k] * x[k], c.g[k] * (S - incl), incl - x[k], Z);
     }
+}
+// The three addends of T^T x - stay, from above, from below - handed to `sink(k, stay, down, up)`.
+template <int NPL, typename Sink>
+__device__ __forceinline__ void pt_fwd_addends(const SsFwdC<NPL> &c, double c0, const double (&x)[NPL], double &S, Sink sink) {
+    pt_fwd_parts<NPL>(c, x, S, [&](int k, double s0, double s1, double low, double Z) { sink(k, s0, s1, __builtin_fma(c0, low, Z)); });
 }
 
 template <int NPL>

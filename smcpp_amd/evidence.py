@@ -59,15 +59,20 @@ def compare_tracks(track_a, track_b, block=1):
 
 
 def score_track(model, contigs, M, n, theta, rho, window, alpha=1.0, polarization_error=0.5, a=None, device=-1, return_manager=False,
-                seeds=None):
+                seeds=None, form=None):
     """The score of every contig under `model`, per window of `window` base pairs: d loglik / d direction, window by window
     (`im.score_windows`, include/smcpp_engine.h: smcpp_score_windows).  Built like `loglik_track` - `M` the number of hidden states
-    (at most 64) or their break points, one manager, the missing row in front of every contig - but on ONE `save_gamma` E-step, and
+    (at most 64; at most 256 with `form="vectors"`) or their break points, one manager, the missing row in front of every contig - but on ONE `save_gamma` E-step, and
     the model has to carry derivative seeds: `PiecewiseModel.differentiable = True` (one direction per piece), an
     `AdPiecewiseModel`'s `dlist`, or `seeds`, a `[pieces, nder]` array d a_k / d x_j for a one-population model (it replaces the
     model's own).  Returns `(hidden_states, track)`, `track[c]` the `[nder, ceil(P_c / window)]` window values of contig c; summed
     over windows and contigs they are the gradient of the log-likelihood in those directions.  `return_manager=True` appends the
-    inference manager."""
+    inference manager.  `form`: "matrix" or "vectors", the form of the engine's row walk (SMCPP_SCORE_FORM, set around this
+    function's own score calls and put back afterwards; None: whatever the environment says, the matrix form when it says nothing).
+    The vectors form serves one-population models up to 256 hidden states; a manager that is kept answers later calls in the form
+    the switch names then."""
+    if form not in (None, "matrix", "vectors"):
+        raise ValueError(f"score_track: form {form!r} (expected None, 'matrix' or 'vectors')")
     hidden_states = None if np.isscalar(M) else np.asarray(M, dtype=float)
     nstates = int(M) if hidden_states is None else len(hidden_states) - 1
     if seeds is not None:
@@ -82,7 +87,17 @@ def score_track(model, contigs, M, n, theta, rho, window, alpha=1.0, polarizatio
         model.derivative_seeds = lambda: seeds
     hs, obs, im = _decode_setup(model, contigs, nstates, n, theta, rho, alpha, polarization_error, hidden_states, device, a, None, None, 1,
                                 save_gamma=True)
-    track = [im.score_windows(c, int(window)) for c in range(len(obs))]
+    if form is None:
+        track = [im.score_windows(c, int(window)) for c in range(len(obs))]
+    else:
+        import os
+        from . import _engine
+        before = os.environ.get("SMCPP_SCORE_FORM")
+        _engine.set_option("SMCPP_SCORE_FORM", form)
+        try:
+            track = [im.score_windows(c, int(window)) for c in range(len(obs))]
+        finally:
+            _engine.set_option("SMCPP_SCORE_FORM", before)
     if return_manager:
         return hs, track, im
     return hs, track

@@ -1,18 +1,21 @@
-"""What the score track costs beside the `save_gamma` E-step and the posterior transition products of the same run.
+"""What the score track costs, in both forms of its row walk, beside the `save_gamma` E-step and the posterior transition products
+of the same run.
 
-Two inputs, one manager each, in one process, the model differentiable in every piece (16 directions):
+Three inputs, one manager each, in one process, the model differentiable in every piece (16 directions):
 
-  binned100M_M64  the binned 100 Mbp contig at M = 64, n = 20 (rows of 100 bp bins): short rows, the per-row contraction dominates
-  posterior64     the input of `bench.py --workload posterior64` cut to --rows rows: M = 64, n = 8, un-binned
-                  (`synth_posterior_contig`): rows of up to 10^5 positions, the walk dominates
+  binned100M_M64   the binned 100 Mbp contig at M = 64, n = 20 (rows of 100 bp bins): short rows, the per-row contraction dominates
+  posterior64      the input of `bench.py --workload posterior64` cut to --rows rows: M = 64, n = 8, un-binned
+                   (`synth_posterior_contig`): rows of up to 10^5 positions, the walk dominates
+  binned100M_M256  the binned contig at M = 256 (four states per lane): the vectors form alone, the matrix form stops at 64 states
 
 Per input: two `save_gamma` E-steps to settle, then `--repeats` rounds after `--warmup` of (a) the E-step (with its 16-direction
-preparation), wall clock up to the log-likelihood on the host, (b) `posterior_transitions(0)`, (c) `score_rows(0)`,
-(d) `score_rows(0, parts=True)`, (e) `score_windows(0, W)`; every call ends in a device synchronise and a copy to the host.  The first
-score call behind an E-step also builds and uploads the tables (G_pi, dT, G_E); it is timed apart as `score_first_call_ms`.  Reported
-per leg: the minimum, the median and the spread (max - min); the launch shape (`score_items`, `score_waves`, `score_park`; read once,
-outside the timed rounds), the ratios (c) / (b) and (c) / (a), and how far the score's sum lies from Q's gradient.
-One JSON line per input, to stdout and appended to --out.
+preparation), wall clock up to the log-likelihood on the host, (b) `posterior_transitions(0)`, and per form (SMCPP_SCORE_FORM set
+through `_engine.set_option` around the leg) (c) `score_rows(0)`, (d) `score_rows(0, parts=True)`, (e) `score_windows(0, W)`; every
+call ends in a device synchronise and a copy to the host.  The forms alternate inside every round, so they see the same machine.  The
+first score call of a form behind an E-step also builds and uploads its tables; it is timed apart as `first_call_ms`.  Reported per
+leg: the minimum, the median and the spread (max - min); per form the launch shape (`score_items`, `score_waves`, `score_park`; read
+once, outside the timed rounds), the ratios of (c) to (b), to (a) and to the matrix form's (c) of the same run, and how far the
+score's sum lies from Q's gradient.  One JSON line per input, to stdout and appended to --out.
 
     python tools/score_track_probe.py [--rows N] [--repeats K] [--warmup W] [--window BP] [--only NAME] [--out FILE]
 """
@@ -44,10 +47,11 @@ def main():
     def posterior64():
         return 64, 8, synth.synth_posterior_contig(args.rows, 8, seed=7), 2e-4, 6e-5
 
-    def binned():
-        return 64, 20, np.ascontiguousarray(synth.synth_contig(0, 100_000_000, 20), dtype=np.int32), synth.THETA, synth.RHO
+    def binned(M):
+        return lambda: (M, 20, np.ascontiguousarray(synth.synth_contig(0, 100_000_000, 20), dtype=np.int32), synth.THETA, synth.RHO)
 
-    inputs = {"binned100M_M64": binned, "posterior64": posterior64}
+    from smcpp_amd import _engine
+    inputs = {"binned100M_M64": binned(64), "posterior64": posterior64, "binned100M_M256": binned(256)}
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         if not args.only:                  # (a run of one input appends its line)
@@ -65,13 +69,28 @@ def main():
         im.E_step()
         im.E_step()
         im.loglik()
-        t0 = time.perf_counter()
-        im.score_rows(0)
-        first = 1e3 * (time.perf_counter() - t0)
+        forms = ("matrix", "vectors") if M <= 64 else ("vectors",)
 
-        legs = {"estep_save_gamma": None, "posterior_transitions": lambda: im.posterior_transitions(0),
-                "score_rows": lambda: im.score_rows(0), "score_rows_parts": lambda: im.score_rows(0, parts=True),
-                "score_windows": lambda: im.score_windows(0, args.window)}
+        def in_form(form, f):
+            def call():
+                _engine.set_option("SMCPP_SCORE_FORM", form)
+                try:
+                    return f()
+                finally:
+                    _engine.set_option("SMCPP_SCORE_FORM", None)
+            return call
+
+        first = {}
+        for form in forms:
+            t0 = time.perf_counter()
+            in_form(form, lambda: im.score_rows(0))()
+            first[form] = 1e3 * (time.perf_counter() - t0)
+
+        legs = {"estep_save_gamma": None, "posterior_transitions": lambda: im.posterior_transitions(0)}
+        for form in forms:
+            legs[form + ":score_rows"] = in_form(form, lambda: im.score_rows(0))
+            legs[form + ":score_rows_parts"] = in_form(form, lambda: im.score_rows(0, parts=True))
+            legs[form + ":score_windows"] = in_form(form, lambda: im.score_windows(0, args.window))
         times = {k: [] for k in legs}
         for r in range(args.warmup + args.repeats):
             for k, f in legs.items():
@@ -83,25 +102,30 @@ def main():
                     f()
                 dt = 1e3 * (time.perf_counter() - t0)
                 if f is None:
-                    im.score_rows(0, 0, 1)  # (the tables of this E-step: built here, outside the score legs)
+                    for form in forms:      # (the tables of this E-step: built here, outside the score legs)
+                        in_form(form, lambda: im.score_rows(0, 0, 1))()
                 if r >= args.warmup:
                     times[k].append(dt)
-        rows = im.score_rows(0, parts=True)
         _, jac = im.Q_with_gradient()
-        d = im.describe()                   # (the launch shape of the last score call; the route of the Q behind it)
         m0 = float(im.posterior_columns(0, 0, 1, normalize=False).sum())       # (Q weighs log pi with the stored, unnormalised column 0)
         want = np.stack([jac[0] / m0, jac[1] + jac[2], jac[3]])
-        off = float(np.max(np.abs(rows.sum(axis=2) - want) / np.maximum(np.abs(rows).sum(axis=2), 1e-300)))
-        plan = d["plan"]
         best = {k: min(v) for k, v in times.items()}
+        per_form = {}
+        for form in forms:
+            rows = in_form(form, lambda: im.score_rows(0, parts=True))()
+            d = im.describe()               # (the launch shape of the last score call; the route of the Q behind it)
+            per_form[form] = {
+                "launch": {"score_items": d["score_items"], "score_waves": d["score_waves"], "score_park": d["score_park"], "score_form": d["score_form"]},
+                "first_call_ms": round(first[form], 3),
+                "score_rows_over_posterior_transitions": round(best[form + ":score_rows"] / best["posterior_transitions"], 3),
+                "score_rows_over_estep": round(best[form + ":score_rows"] / best["estep_save_gamma"], 3),
+                "score_rows_over_matrix_form": round(best[form + ":score_rows"] / best["matrix:score_rows"], 3) if "matrix" in forms else None,
+                "parts_sum_off_q_jacobian_rel": float(np.max(np.abs(rows.sum(axis=2) - want) / np.maximum(np.abs(rows).sum(axis=2), 1e-300)))}
+        plan = d["plan"]
         res = {"input": name, "M": M, "directions": int(rows.shape[1]), "rows": len(contig), "positions": int(contig[:, 0].astype(np.int64).sum()),
                "longest_row": int(contig[:, 0].max()), "window": args.window, "repeats": args.repeats,
                "plan": {k: plan[k] for k in ("chain_family", "states_per_lane", "long_rows_cut", "hybrid_rows")},
-               "launch": {"score_items": d["score_items"], "score_waves": d["score_waves"], "score_park": d["score_park"]},
-               "q_route": d["q_route"], "score_first_call_ms": round(first, 3),
-               "score_rows_over_posterior_transitions": round(best["score_rows"] / best["posterior_transitions"], 3),
-               "score_rows_over_estep": round(best["score_rows"] / best["estep_save_gamma"], 3),
-               "parts_sum_off_q_jacobian_rel": off,
+               "q_route": d["q_route"], "forms": per_form,
                "legs": {k: {"min_ms": round(min(v), 3), "median_ms": round(float(np.median(v)), 3), "spread_ms": round(max(v) - min(v), 3)}
                         for k, v in times.items()}}
         line = json.dumps(res)
