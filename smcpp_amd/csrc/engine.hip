@@ -38,6 +38,7 @@
 #include "prep.hpp"
 #include "prep_dev.hpp"
 #include "jcsfs.hpp"
+#include "walk_dev.hpp"         // what the product kernels that walk a row share: the rows, the lane layout, the checkpoints
 #include "posterior_dev.hpp"    // products of the per-row posteriors: columns, per-column summaries, windows
 #include "posterior_trans_dev.hpp"   // posterior transition products: stay / up / down per row and per window
 #include "score_track_dev.hpp"       // score track: d loglik / d direction per row (initial, emission, transition part) and per window

@@ -314,6 +314,7 @@ struct smcpp_im {
     // E-step, uploaded by every walking call), the host-side set-up of a walk over the stored vectors
     DevBuf<double> d_walk_gen;
     SsArgs walk_generators();                     // ss_gen -> d_walk_gen on `stream`; a fresh SsArgs with M, Mp and the generators set
+    WalkRows walk_rows(int c);                    // the stored vectors and the row table a walk over contig c reads
     int longest_row(int c);                       // the longest engine row of contig c
     long long walk_slots() const;                 // wavefront slots of a persistent walk
     const long long *user_prefix_dev(int c);      // user_prefix[c] on the device, uploaded on first use

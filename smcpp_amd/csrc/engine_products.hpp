@@ -39,6 +39,14 @@ SsArgs smcpp_im::walk_generators() {
     return sa;
 }
 
+// The rows a walk over contig c reads: the stored vectors of the last E-step and its row table (walk_dev.hpp).
+WalkRows smcpp_im::walk_rows(int c) {
+    WalkRows w;
+    w.M = M; w.Mp = Mp; w.base = contig_base[c];
+    w.rowinfo = d_rowinfo.p; w.g_span = d_g_span.p; w.E = d_E.p; w.alpha = d_alpha.p; w.beta = d_beta.p;
+    return w;
+}
+
 // The longest engine row of contig c (1: it has none), and the fp64 checkpoints a walk in blocks of `blk` positions keeps of such a row.
 int smcpp_im::longest_row(int c) {
     int smax = 1;
@@ -272,7 +280,7 @@ const double *smcpp_im::post_transitions(int c, long long start, long long step,
     const int *first = piece_first_dev(c);
     const SsArgs sa = walk_generators();
     PtArgs pa;
-    pa.M = M; pa.Mp = Mp; pa.L = Le; pa.base = contig_base[c];
+    pa.w = walk_rows(c); pa.L = Le;
     pa.nck = walk_checkpoints(longest_row(c), PT_BLK);
     // one wavefront per row, persistent; fewer of them where the scratch of a wavefront is large (many states per lane, or the
     // checkpoints of a very long row): at most 1 GiB in all
@@ -281,7 +289,6 @@ const double *smcpp_im::post_transitions(int c, long long start, long long step,
     d_pt_park.alloc((size_t)nw * PT_BLK * 3 * MS);
     d_pt_ckpt.alloc(std::max<size_t>(1, (size_t)nw * pa.nck * MS));
     d_pt_eng.alloc((size_t)3 * (Le + 1));
-    pa.rowinfo = d_rowinfo.p; pa.g_span = d_g_span.p; pa.E = d_E.p; pa.alpha = d_alpha.p; pa.beta = d_beta.p;
     pa.park = d_pt_park.p; pa.ckpt = d_pt_ckpt.p; pa.out = d_pt_eng.p;
     pt_waves = nw;
     const dim3 grid(ceil_div(nw, 4)), block(256);
@@ -844,8 +851,8 @@ void smcpp_im::ll_table(int c, long long pos0, long long pos1, long long step, b
 void smcpp_im::ll_walk(int c, long long step, double *slots) {
     const SsArgs sa = walk_generators();
     LlArgs la = LlArgs();
-    la.M = M; la.Mp = Mp; la.nitems = (int)ll_items.size(); la.base = contig_base[c];
-    la.rowinfo = d_rowinfo.p; la.g_span = d_g_span.p; la.E = d_E.p; la.alpha = d_alpha.p; la.logc = d_logc.p; la.pre = d_ll_pre.p;
+    la.w = walk_rows(c); la.w.beta = nullptr;          // (forward only: whether the last E-step kept beta does not matter)
+    la.nitems = (int)ll_items.size(); la.logc = d_logc.p; la.pre = d_ll_pre.p;
     d_ll_items.upload(ll_items, stream);               // (a member: it outlives the copy)
     d_ll_ratio.alloc((size_t)la.nitems);
     la.items = d_ll_items.p; la.step = step; la.out = slots; la.ratio = d_ll_ratio.p;
@@ -1124,14 +1131,13 @@ void smcpp_im::score_rows_matrix(int c, int nck) {
     const int Le = Ls[c];
     const SsArgs sa = walk_generators();               // (one state per lane: score_check)
     ScArgs a = ScArgs();
-    a.M = M; a.Mp = Mp; a.L = Le; a.nck = nck; a.nder = nder; a.base = contig_base[c];
+    a.w = walk_rows(c); a.L = Le; a.nck = nck; a.nder = nder;
     // one wavefront per engine row, persistent: a workgroup's parked vectors fill a CU's LDS, so 4 wavefronts per CU are resident;
     // fewer where SMCPP_SCORE_WAVES says so or the checkpoints of a very long row would pass 1 GiB with the parts
     const size_t left = (1ull << 30) - (size_t)3 * nder * ((size_t)Le + 1) * sizeof(double);       // (not negative: score_check)
     long long nw = walk_waves(Le, 1024, (size_t)nck * 64 * sizeof(double), left);   // (a contig without rows: wavefront 0 writes column 0)
     if (opt().has(smcpp_opt::O_SCORE_WAVES)) nw = std::min(nw, std::max<long long>(1, opt().ll(smcpp_opt::O_SCORE_WAVES, 1)));
     d_sc_ckpt.alloc(std::max<size_t>(1, (size_t)nw * nck * 64));
-    a.rowinfo = d_rowinfo.p; a.g_span = d_g_span.p; a.E = d_E.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
     a.gamma0 = d_gamma0.p + (size_t)c * Mp;
     a.Gpi = d_sc_tab.p; a.dT = a.Gpi + (size_t)nder * 64; a.GE = a.dT + (size_t)nder * 64 * 64;
     a.ckpt = d_sc_ckpt.p; a.out = d_sc_eng.p;

@@ -1,6 +1,7 @@
 // loglik_track_dev.hpp - the log-likelihood TRACK of the last E-step: l(p) = log P(o_1 .. o_p) per caller's row, per position of a
-// grid and per window ("Log-likelihood track").  Included from engine.hip behind posterior_pos_dev.hpp; the host side is
-// in engine_products.hpp (smcpp_loglik_rows / _positions / _windows).  Forward quantities only: the stored float alpha and log c of
+// grid and per window ("Log-likelihood track").  Included from engine.hip behind walk_dev.hpp (the leaves of the row
+// walk) and posterior_pos_dev.hpp; the host side is in engine_products.hpp (smcpp_loglik_rows / _positions / _windows).
+// Forward quantities only: the stored float alpha and log c of
 // every engine row, which every E-step leaves behind - save_gamma is not needed, and the posterior buffers are not touched.
 //
 // Positions 0 .. N of a contig (0 = column 0; engine row r covers the `span` positions behind EP[r - 1], EP = the position prefix
@@ -120,13 +121,8 @@ struct LlItem {
 };
 
 struct LlArgs {
-    int M, Mp;
+    WalkRows w;                 // (forward only: beta is null)
     int nitems;
-    long long base;             // global row of the contig's row 0
-    const RowInfo *rowinfo;     // [global rows] {key id, group id or -1}
-    const int *g_span;          // [groups]
-    const double *E;            // [K][Mp]
-    const float *alpha;         // [global rows][Mp] stored forward vectors (row r: at the END of row r)
     const double *logc;         // [global rows]
     const double *pre;          // [Le + 1] of this contig
     const LlItem *items;        // [nitems]
@@ -145,46 +141,30 @@ __global__ __launch_bounds__(256) void k_ll_walk(SsArgs sa, LlArgs a, int nwaves
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= nwaves) return;
-    const int M = a.M, Mp = a.Mp;
+    const int M = a.w.M;
     SsFwdC<NPL> c;
     ss_load_fwd<NPL>(sa, lane, c);
     for (int it = gw; it < a.nitems; it += nwaves) {
         const LlItem item = a.items[it];
         const int r = ss_uni(item.row), nq = ss_uni(item.nq);
         const long long q0 = ll_uni(item.q0), seg = ll_uni(item.seg), first = ll_uni(item.first);
-        const size_t row = (size_t)(a.base + r);
-        const int kid = ss_uni(a.rowinfo[row].kid), gid = ss_uni(a.rowinfo[row].gid);
-        const int span = gid < 0 ? 1 : ss_uni(a.g_span[gid]);
-        const double *ek = a.E + (size_t)kid * Mp;
-        const float *ap = a.alpha + (row - 1) * Mp;                        // the plain stored vector (DESIGN.md says why)
-        double x[NPL], ev[NPL], part = 0.0;
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            const int s = lane * NPL + k;
-            const bool live = s < M;
-            x[k] = live ? (double)ap[live ? s : 0] : 0.0;
-            ev[k] = live ? ek[live ? s : 0] : 0.0;
-            part += x[k];
-        }
-        const double i0 = 1.0 / wave_sum_dpp(part);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) x[k] *= i0;
+        const WalkRow wr = walk_row(a.w, r);
+        const size_t row = wr.row;
+        const int span = wr.span;
+        double x[NPL], ev[NPL];
+        walk_load_norm<NPL>(wr.ap, M, lane, x);                            // the plain stored vector (DESIGN.md says why)
+        walk_load<NPL>(wr.ek, M, lane, ev);
         double acc = 0.0, As = 0.0;                                        // acc = - log S_0 - sum_t log inv_t
         long long qn = first - q0;                                         // the in-row offset of the next query
         int cnt = 0;
         for (int t = 1; t <= span; ++t) {
             double out[NPL], S;
             ss_fwd_step<NPL>(c, x, ev, out, S);
-            const float invf = __builtin_amdgcn_rcpf((float)S);
-            const double inv = (double)invf;
-            acc -= log(inv);
+            acc -= log(walk_rescale<NPL>(x, out, (float)S));
             if (t == 1) acc -= log(S);
             double px = 0.0;
 #pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                x[k] = out[k] * inv;
-                px += x[k];
-            }
+            for (int k = 0; k < NPL; ++k) px += x[k];
             const bool query = cnt < nq && (long long)t == qn;
             if (query || t == span) {
                 const double A = log(wave_sum_dpp(px)) + acc;
@@ -196,7 +176,7 @@ __global__ __launch_bounds__(256) void k_ll_walk(SsArgs sa, LlArgs a, int nwaves
                 As = A;                                                    // (the last one stands: t == span)
             }
         }
-        // the slots are read back by OTHER lanes of this wavefront: the stores have to be acknowledged first (as in k_post_positions)
+        // the slots are read back by OTHER lanes of this wavefront: the stores have to be acknowledged first
         __threadfence_block();
         const double lc = a.logc[row], l0 = a.pre[r - 1];
         for (int u = lane; u < nq; u += 64) {

@@ -1,6 +1,8 @@
 // posterior_paths_dev.hpp - joint draws of the hidden-state path from the posterior of the last save_gamma E-step, by forward
 // filtering and backward sampling ("Posterior paths").  Included from engine.hip behind posterior_trans_dev.hpp (whose
-// row walk - blocks of 64 positions, fp64 checkpoints of long rows - is repeated here); the host side is in engine_products.hpp
+// row walk - blocks of 64 positions, fp64 checkpoints of long rows - is repeated here BY HAND, not through the leaves of
+// walk_dev.hpp: with them k_post_paths compiles to other code at every state count, 0.5 - 2.5 % slower where it was measured and
+// with another scratch size at 16 states per lane; profiles/walk_leaves_refactor.log); the host side is in engine_products.hpp
 // (smcpp_posterior_sample_rows / _sample_positions).
 //
 // Positions 0 .. N of a contig (0 = column 0, engine row r covers the `span` positions behind the end of row r - 1), forward vectors

@@ -1,7 +1,8 @@
 // posterior_pos_dev.hpp - per-POSITION posterior products of the last save_gamma E-step: the marginal gamma_p of single positions on a
 // grid, its summaries, and the window averages that are exact on long rows ("Posterior positions").  Included from
-// engine.hip behind posterior_trans_dev.hpp (pt_add, the row walk repeated here) and posterior_paths_dev.hpp; the host side is in
-// engine_products.hpp (smcpp_posterior_positions / _position_summary / _windows_exact).
+// engine.hip behind walk_dev.hpp (pt_add), posterior_trans_dev.hpp (the row walk, repeated here BY HAND: with the leaves of walk_dev.hpp
+// the scratch of k_post_positions at 16 states per lane moves by up to 50 %; profiles/walk_leaves_refactor.log) and
+// posterior_paths_dev.hpp; the host side is in engine_products.hpp (smcpp_posterior_positions / _position_summary / _windows_exact).
 //
 // Positions 0 .. N of a contig (0 = column 0, engine row r covers the `span` positions behind the end of row r - 1):
 //     a_0 = pi, a_p = e_p o (T^T a_{p-1}),   b_N = 1, b_{p-1} = T (e_p o b_p),   gamma_p(i) = a_p(i) b_p(i) / sum_m a_p(m) b_p(m).

@@ -1,7 +1,7 @@
 // posterior_trans_dev.hpp - posterior TRANSITION products of the last save_gamma E-step: per row and per window the expected number of
 // positions at which the hidden state stays, moves up (to a higher index = older state) or moves down ("Posterior
-// transition products").  Included from engine.hip behind chains_ss.hpp (the scan steps) and posterior_dev.hpp (PostSel); the host
-// side is in engine_products.hpp (smcpp_posterior_transitions / _transition_windows).
+// transition products").  Included from engine.hip behind chains_ss.hpp (the scan steps), walk_dev.hpp (the leaves of a row walk)
+// and posterior_dev.hpp (PostSel); the host side is in engine_products.hpp (smcpp_posterior_transitions / _transition_windows).
 //
 // For a position p of a row with emission vector e, forward vector x_{p-1} before it and backward vector y_p after it,
 //     xi_p(i, j) = x_{p-1}(i) T(i, j) e(j) y_p(j) / Z_p,     stay = sum_i xi(i, i),  up = sum_{i<j} xi(i, j),  down = sum_{i>j} xi(i, j).
@@ -27,22 +27,10 @@
 
 namespace smcpp_dev {
 
-// s += v with the rounding error of the addition kept in c (Neumaier's form of Kahan's sum; the total is s + c)
-__device__ __forceinline__ void pt_add(double &s, double &c, double v) {
-    const double t = s + v;
-    c += (fabs(s) >= fabs(v)) ? (s - t) + v : (v - t) + s;
-    s = t;
-}
-
 struct PtArgs {
-    int M, Mp, L;               // L: ENGINE rows of the contig (rows 1 .. L; row 0 is column 0)
+    WalkRows w;
+    int L;                      // ENGINE rows of the contig (rows 1 .. L; row 0 is column 0)
     int nck;                    // checkpoint vectors per wavefront (blocks of the longest row - 1)
-    long long base;             // global row of the contig's row 0
-    const RowInfo *rowinfo;     // [global rows] {key id, group id or -1}
-    const int *g_span;          // [groups]
-    const double *E;            // [K][Mp]
-    const float *alpha;         // [global rows][Mp] stored forward vectors (row r: at the END of row r)
-    const double *beta;         // [global rows][Mp] stored backward vectors (row r: at the END of row r)
     float *park;                // [wavefronts][64][3][MS]
     double *ckpt;               // [wavefronts][nck][MS]
     double *out;                // [3][L + 1]
@@ -95,62 +83,40 @@ __global__ __launch_bounds__(256) void k_post_transitions(SsArgs sa, PtArgs a, i
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= nwaves) return;
-    const int M = a.M, Mp = a.Mp;
+    const int M = a.w.M;
     const size_t LD = (size_t)a.L + 1;
     float *park = a.park + (size_t)gw * PT_BLK * 3 * MS;
     double *ckpt = a.ckpt + (size_t)gw * a.nck * MS;
     if (gw == 0 && lane < 3) a.out[lane * LD] = 0.0;                       // column 0: no transition enters it
     for (int r = 1 + gw; r <= a.L; r += nwaves) {
-        const size_t row = (size_t)(a.base + r);
-        const int kid = ss_uni(a.rowinfo[row].kid), gid = ss_uni(a.rowinfo[row].gid);
-        const int span = gid < 0 ? 1 : ss_uni(a.g_span[gid]);
-        const double *ek = a.E + (size_t)kid * Mp;
-        const float *ap = a.alpha + (row - 1) * Mp;
-        const double *bp = a.beta + row * Mp;
+        const WalkRow wr = walk_row(a.w, r);
+        const int span = wr.span;
         const int nblk = (span + PT_BLK - 1) / PT_BLK;
         // ---- rows of more than one block: x at the start of blocks 1 .. nblk - 1 ----
         if (nblk > 1) {
             SsFwdC<NPL> c;
             ss_load_fwd<NPL>(sa, lane, c);
+            // (x and e in ONE hand-written loop, and the backward walk's e with its state table below: with the leaves of walk_dev.hpp
+            // in these two places the kernel passes 168 registers at four states per lane, and a third wavefront per SIMD is lost)
             double x[NPL], ev[NPL], part = 0.0;
 #pragma unroll
             for (int k = 0; k < NPL; ++k) {
                 const int st = lane * NPL + k;
                 const bool live = st < M;
-                x[k] = live ? (double)ap[live ? st : 0] : 0.0;
-                ev[k] = live ? ek[live ? st : 0] : 0.0;
+                x[k] = live ? (double)wr.ap[live ? st : 0] : 0.0;
+                ev[k] = live ? wr.ek[live ? st : 0] : 0.0;
                 part += x[k];
             }
             const double i0 = 1.0 / wave_sum_dpp(part);
 #pragma unroll
             for (int k = 0; k < NPL; ++k) x[k] *= i0;
-            for (int b = 1; b < nblk; ++b) {
-                for (int t = 0; t < PT_BLK; ++t) {
-                    double out[NPL], S;
-                    pt_fwd_addends<NPL>(c, sa.c0, x, S, [&](int k, double s0, double s1, double s2) { out[k] = ev[k] * (s0 + s1 + s2); });
-                    const double inv = (double)__builtin_amdgcn_rcpf((float)S);            // (a rescaling only: it cancels)
-#pragma unroll
-                    for (int k = 0; k < NPL; ++k) x[k] = out[k] * inv;
-                }
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) ckpt[(size_t)(b - 1) * MS + lane * NPL + k] = x[k];
-            }
+            walk_checkpoints<NPL, PT_BLK>(x, ckpt, nblk, lane, [&](const double (&u)[NPL], double (&out)[NPL], double &S) {
+                pt_fwd_addends<NPL>(c, sa.c0, u, S, [&](int k, double s0, double s1, double s2) { out[k] = ev[k] * (s0 + s1 + s2); });
+            });
         }
         // ---- the blocks, last to first: y carried in a running scale across them ----
         double h[NPL];
-        {
-            double part = 0.0;
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                const int st = MS - 1 - (lane * NPL + k);
-                const bool live = st < M;
-                h[k] = live ? bp[live ? st : 0] : 0.0;
-                part += h[k];
-            }
-            const double i0 = 1.0 / wave_sum_dpp(part);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) h[k] *= i0;
-        }
+        walk_load_norm<NPL, true>(a.w.beta + wr.row * a.w.Mp, M, lane, h);
         double acc[3] = {0.0, 0.0, 0.0}, cmp[3] = {0.0, 0.0, 0.0};
         for (int b = nblk - 1; b >= 0; --b) {
             const int len = min(PT_BLK, span - b * PT_BLK);
@@ -159,28 +125,8 @@ __global__ __launch_bounds__(256) void k_post_transitions(SsArgs sa, PtArgs a, i
                 SsFwdC<NPL> c;
                 ss_load_fwd<NPL>(sa, lane, c);
                 double x[NPL], ev[NPL];
-                if (b == 0) {
-                    double part = 0.0;
-#pragma unroll
-                    for (int k = 0; k < NPL; ++k) {
-                        const int st = lane * NPL + k;
-                        const bool live = st < M;
-                        x[k] = live ? (double)ap[live ? st : 0] : 0.0;
-                        part += x[k];
-                    }
-                    const double i0 = 1.0 / wave_sum_dpp(part);
-#pragma unroll
-                    for (int k = 0; k < NPL; ++k) x[k] *= i0;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < NPL; ++k) x[k] = ckpt[(size_t)(b - 1) * MS + lane * NPL + k];
-                }
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) {
-                    const int st = lane * NPL + k;
-                    const bool live = st < M;
-                    ev[k] = live ? ek[live ? st : 0] : 0.0;
-                }
+                walk_block_start<NPL>(wr.ap, ckpt, b, M, lane, x);
+                walk_load<NPL>(wr.ek, M, lane, ev);
                 for (int t = 0; t < len; ++t) {
                     double out[NPL], S;
                     float *pk = park + (size_t)t * 3 * MS + lane * NPL;
@@ -190,9 +136,7 @@ __global__ __launch_bounds__(256) void k_post_transitions(SsArgs sa, PtArgs a, i
                         pk[k] = (float)s0; pk[MS + k] = (float)s1; pk[2 * MS + k] = (float)s2;
                         out[k] = ev[k] * (s0 + s1 + s2);
                     });
-                    const double inv = (double)__builtin_amdgcn_rcpf((float)S);
-#pragma unroll
-                    for (int k = 0; k < NPL; ++k) x[k] = out[k] * inv;
+                    walk_rescale<NPL>(x, out, (float)S);
                 }
             }
             // the parked addends are read back by OTHER lanes of this wavefront (reversed state order): the stores have to be
@@ -207,7 +151,7 @@ __global__ __launch_bounds__(256) void k_post_transitions(SsArgs sa, PtArgs a, i
                 for (int k = 0; k < NPL; ++k) {
                     st[k] = MS - 1 - (lane * NPL + k);
                     const bool live = st[k] < M;
-                    ev[k] = live ? ek[live ? st[k] : 0] : 0.0;
+                    ev[k] = live ? wr.ek[live ? st[k] : 0] : 0.0;
                 }
                 for (int t = len - 1; t >= 0; --t) {
                     const float *pk = park + (size_t)t * 3 * MS;
@@ -228,9 +172,7 @@ __global__ __launch_bounds__(256) void k_post_transitions(SsArgs sa, PtArgs a, i
                         double out[NPL];
                         float Sw;
                         ss_bwd_step<NPL>(c, h, ev, out, Sw);
-                        const double is = (double)__builtin_amdgcn_rcpf(Sw);      // (a rescaling only)
-#pragma unroll
-                        for (int k = 0; k < NPL; ++k) h[k] = out[k] * is;
+                        walk_rescale<NPL>(h, out, Sw);
                     }
                 }
             }

@@ -1,6 +1,6 @@
 // score_track_dev.hpp - the SCORE track of the last save_gamma E-step: per row and per window the derivative of the log-likelihood
-// with respect to every seeded direction of the model ("Score track").  Included from engine.hip behind
-// posterior_trans_dev.hpp (pt_add, pt_fwd_addends, the blocked walk this one follows) and posterior_dev.hpp (PostSel); the host side
+// with respect to every seeded direction of the model ("Score track").  Included from engine.hip behind walk_dev.hpp
+// (pt_add, the leaves of the row walk), posterior_trans_dev.hpp (pt_fwd_addends) and posterior_dev.hpp (PostSel); the host side
 // is in engine_products.hpp (smcpp_score_rows / _windows).
 //
 // For a position p of a row with key k, emission vector e = E[k], forward vector x_{p-1} before it and backward vector y_p after it,
@@ -15,7 +15,8 @@
 //   k_score_select    the pieces of a caller's row added up, a column selection taken: [3][nder][ncols] or the total [nder][ncols]
 //   k_score_windows   [nder][n_windows]: a row apportioned uniformly over its base pairs, one wavefront per window
 //
-// The walk is k_post_transitions<1>'s: blocks of at most 64 positions, fp64 checkpoints of x at the block starts of longer rows,
+// The walk is k_post_transitions<1>'s, on the same leaves (walk_dev.hpp): blocks of at most 64 positions, fp64 checkpoints of x
+// at the block starts of longer rows,
 // forward from the stored float alpha, backward from the stored beta, rescaled at every step (every position is normalised by its
 // own Z_p).  The forward walk of a block parks x_{p-1} and T^T x_{p-1} of every position as floats in the wavefront's own 32 KB of
 // LDS (four wavefronts of a workgroup: 128 of the 160 KB); the backward walk reads T^T x_{p-1} at its own state (Z_p and gamma_p
@@ -30,15 +31,10 @@
 namespace smcpp_dev {
 
 struct ScArgs {
-    int M, Mp, L;               // L: ENGINE rows of the contig (rows 1 .. L; row 0 is column 0)
+    WalkRows w;
+    int L;                      // ENGINE rows of the contig (rows 1 .. L; row 0 is column 0)
     int nck;                    // checkpoint vectors per wavefront (blocks of the longest row - 1)
     int nder;                   // directions
-    long long base;             // global row of the contig's row 0
-    const RowInfo *rowinfo;     // [global rows] {key id, group id or -1}
-    const int *g_span;          // [groups]
-    const double *E;            // [K][Mp]
-    const float *alpha;         // [global rows][Mp] stored forward vectors (row r: at the END of row r)
-    const double *beta;         // [global rows][Mp] stored backward vectors (row r: at the END of row r)
     const double *gamma0;       // [Mp] the contig's column 0 as stored (proportional to gamma_0)
     const double *Gpi;          // [nder][64]      dpi_d / pi, zero beyond M
     const double *dT;           // [nder][64][64]  dT_d(i, j), j fastest, zero beyond M
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(256) void k_score_rows(SsArgs sa, ScArgs a, int nwa
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (gw >= nwaves) return;                                    // (no workgroup barrier below: the LDS of a wavefront is its own)
-    const int M = a.M, Mp = a.Mp, nder = a.nder;
+    const int M = a.w.M, nder = a.nder;
     const size_t LD = (size_t)a.L + 1;
     float *px = sc_lds + (size_t)(threadIdx.x >> 6) * 2 * SC_BLK * 64;
     float *ptx = px + SC_BLK * 64;
@@ -64,44 +60,34 @@ __global__ __launch_bounds__(256) void k_score_rows(SsArgs sa, ScArgs a, int nwa
     if (gw == 0) {
         // column 0: the initial part alone.  The stored column 0 is the reference's alpha_0 o beta_0 with beta_0 / sum beta_0
         // (hmm.cpp:150): proportional to gamma_0, not normalised - it is normalised here, as every xi_p is by its Z_p
-        const bool live = lane < M;
-        double g0 = live ? a.gamma0[live ? lane : 0] : 0.0;
-        g0 /= wave_sum_dpp(g0);
+        double g0v[1];
+        walk_load<1>(a.gamma0, M, lane, g0v);
+        const double g0 = g0v[0] / wave_sum_dpp(g0v[0]);
         for (int d = 0; d < nder; ++d) {
             const double s = wave_sum_dpp(g0 * a.Gpi[(size_t)d * 64 + lane]);
             if (lane < 3) a.out[((size_t)lane * nder + d) * LD] = lane == 0 ? s : 0.0;
         }
     }
     for (int r = 1 + gw; r <= a.L; r += nwaves) {
-        const size_t row = (size_t)(a.base + r);
-        const int kid = ss_uni(a.rowinfo[row].kid), gid = ss_uni(a.rowinfo[row].gid);
-        const int span = gid < 0 ? 1 : ss_uni(a.g_span[gid]);
-        const double *ek = a.E + (size_t)kid * Mp;
-        const float *ap = a.alpha + (row - 1) * Mp;
-        const double *bp = a.beta + row * Mp;
+        const WalkRow wr = walk_row(a.w, r);
+        const int span = wr.span;
         const int nblk = (span + SC_BLK - 1) / SC_BLK;
-        const bool livef = lane < M, liveb = st < M;
-        const double evf = livef ? ek[livef ? lane : 0] : 0.0, evb = liveb ? ek[liveb ? st : 0] : 0.0;
+        double evf[1], evb[1];
+        walk_load<1>(wr.ek, M, lane, evf);
+        walk_load<1, true>(wr.ek, M, lane, evb);
         // ---- rows of more than one block: x at the start of blocks 1 .. nblk - 1 ----
         if (nblk > 1) {
             SsFwdC<1> c;
             ss_load_fwd<1>(sa, lane, c);
             double x[1];
-            x[0] = livef ? (double)ap[livef ? lane : 0] : 0.0;
-            x[0] *= 1.0 / wave_sum_dpp(x[0]);
-            for (int b = 1; b < nblk; ++b) {
-                for (int t = 0; t < SC_BLK; ++t) {
-                    double tx = 0.0, S;
-                    pt_fwd_addends<1>(c, sa.c0, x, S, [&](int, double s0, double s1, double s2) { tx = s0 + s1 + s2; });
-                    x[0] = evf * tx * (double)__builtin_amdgcn_rcpf((float)S);             // (a rescaling only: it cancels)
-                }
-                ckpt[(size_t)(b - 1) * 64 + lane] = x[0];           // (read back below by the lane that wrote it)
-            }
+            walk_load_norm<1>(wr.ap, M, lane, x);
+            walk_checkpoints<1, SC_BLK>(x, ckpt, nblk, lane, [&](const double (&u)[1], double (&out)[1], double &S) {
+                pt_fwd_addends<1>(c, sa.c0, u, S, [&](int, double s0, double s1, double s2) { out[0] = evf[0] * (s0 + s1 + s2); });
+            });
         }
         // ---- the blocks, last to first: y carried in a running scale across them ----
         double h[1];
-        h[0] = liveb ? bp[liveb ? st : 0] : 0.0;
-        h[0] *= 1.0 / wave_sum_dpp(h[0]);
+        walk_load_norm<1, true>(a.w.beta + wr.row * a.w.Mp, M, lane, h);
         // column `st` of sum_p x_{p-1}(i) w_p(st) / Z_p.  A PLAIN fp64 sum, on purpose: every term is a product of probabilities, none
         // negative, so n positions leave it within n 2^-53 of its value and 64 compensation registers per lane buy nothing.  A change
         // that makes the terms signed (a tangent of x or w in here) has to compensate it, as g below and pt_add's other users are.
@@ -116,17 +102,14 @@ __global__ __launch_bounds__(256) void k_score_rows(SsArgs sa, ScArgs a, int nwa
                 SsFwdC<1> c;
                 ss_load_fwd<1>(sa, lane, c);
                 double x[1];
-                if (b == 0) {
-                    x[0] = livef ? (double)ap[livef ? lane : 0] : 0.0;
-                    x[0] *= 1.0 / wave_sum_dpp(x[0]);
-                } else
-                    x[0] = ckpt[(size_t)(b - 1) * 64 + lane];
+                walk_block_start<1>(wr.ap, ckpt, b, M, lane, x);
                 for (int t = 0; t < len; ++t) {
-                    double tx = 0.0, S;
+                    double out[1], tx = 0.0, S;
                     pt_fwd_addends<1>(c, sa.c0, x, S, [&](int, double s0, double s1, double s2) { tx = s0 + s1 + s2; });
                     px[t * 64 + lane] = (float)x[0];
                     ptx[t * 64 + lane] = (float)tx;
-                    x[0] = evf * tx * (double)__builtin_amdgcn_rcpf((float)S);
+                    out[0] = evf[0] * tx;
+                    walk_rescale<1>(x, out, (float)S);
                 }
             }
             // the parked vectors are read back by OTHER lanes of this wavefront: the LDS stores have to be done first (a wavefront's
@@ -135,9 +118,8 @@ __global__ __launch_bounds__(256) void k_score_rows(SsArgs sa, ScArgs a, int nwa
             {
                 SsBwdC<1> c;
                 ss_load_bwd<1>(sa, lane, c);
-                double ev[1] = {evb};
                 for (int t = len - 1; t >= 0; --t) {
-                    const double w = evb * h[0];
+                    const double w = evb[0] * h[0];
                     const double txv = (double)ptx[t * 64 + st];
                     const double Z = wave_sum_dpp(txv * w);
                     const double q = w / Z;                      // w_p(st) / Z_p
@@ -154,8 +136,8 @@ __global__ __launch_bounds__(256) void k_score_rows(SsArgs sa, ScArgs a, int nwa
                     if (t > 0 || b > 0) {
                         double out[1];
                         float Sw;
-                        ss_bwd_step<1>(c, h, ev, out, Sw);
-                        h[0] = out[0] * (double)__builtin_amdgcn_rcpf(Sw);                 // (a rescaling only)
+                        ss_bwd_step<1>(c, h, evb, out, Sw);
+                        walk_rescale<1>(h, out, Sw);
                     }
                 }
             }
@@ -165,7 +147,7 @@ __global__ __launch_bounds__(256) void k_score_rows(SsArgs sa, ScArgs a, int nwa
         }
         // ---- the contraction: one reduction per direction and part, the states in the wavefront's fixed order ----
         const double gs = g + gc;
-        const double *ge = a.GE + (size_t)kid * nder * 64 + st;
+        const double *ge = a.GE + (size_t)wr.kid * nder * 64 + st;
         for (int d = 0; d < nder; ++d) {
             const double *tb = a.dT + (size_t)d * 64 * 64 + st;
             double p = 0.0;

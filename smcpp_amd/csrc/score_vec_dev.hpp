@@ -15,7 +15,8 @@
 //
 //   k_score_rows_vec<NPL>   one wavefront per ENGINE row: [3][nder][L + 1], the layout of k_score_rows
 //
-// The walk is k_post_transitions<NPL>'s: blocks of at most 64 positions, fp64 checkpoints of x at the block starts of longer rows,
+// The walk is k_post_transitions<NPL>'s, repeated BY HAND (with the leaves of walk_dev.hpp the kernel was 1.5 % slower on long un-binned
+// rows; profiles/walk_leaves_refactor.log): blocks of at most 64 positions, fp64 checkpoints of x at the block starts of longer rows,
 // forward from the stored float alpha, backward from the stored beta, rescaled at every step.  The forward walk of a block parks four
 // floats per position and state in the wavefront's own global scratch (stay | from above | c0 part | Phi' part of the addend from
 // below; Z_p and gamma_p come from the same floats, so a position's gamma sums to one); the backward walk reduces Z_p - ONE wavefront
