@@ -573,6 +573,21 @@ int smcpp_score_rows(smcpp_im *im, int contig, long long start, long long stop, 
  * initial part goes to window 0, in front of the rows.  *n_windows = ceil(P_L / W). */
 int smcpp_score_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
                         double *out /* [nder x n_windows] row-major; NULL: only n_windows */);
+/* smcpp_score_windows_exact: the shape and the windows of smcpp_score_windows, but EXACT on the engine rows that a window boundary
+ * cuts strictly inside (position p >= 1 of the contig lies in window (p - 1) / W): such a row gives every window the sum of u_p over
+ * the positions that lie in it,
+ *     out[d, w] = [w == 0] u_0[d] + sum_{p : (p - 1) / W == w} u_p[d],
+ * what smcpp_score_rows would give on the same data with every row expanded into rows of span 1, added up by window.  Rows that lie
+ * wholly inside a window come from the row walk as before; a cut row is walked a second time by k_score_segments_vec
+ * (score_seg_dev.hpp), which closes a segment at every window boundary; then one wavefront per window adds the rows and segments
+ * that overlap it in ascending position order, compensated.  Values are pure functions of the stored vectors, the tables and W.
+ * The VECTORS form only (M <= 256, under that form's requirements above): with SMCPP_SCORE_FORM unset or "matrix" the call is
+ * refused - set SMCPP_SCORE_FORM=vectors.  SMCPP_SCORE_WAVES caps the wavefronts of the segment walk as well.  Refused besides, as
+ * everything above before any launch: 3 x nder x (segments of cut rows) beyond 2^31 - 1 elements, or the parts per engine row and
+ * per segment with one wavefront's scratch beyond 1 GiB.  smcpp_describe reports "score_exact_items" (the rows a boundary cut),
+ * "score_exact_segments" and "score_exact_waves" (0: no row was cut and the segment walk was not launched) of the last exact call. */
+int smcpp_score_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows,
+                              double *out /* [nder x n_windows] row-major; NULL: only n_windows */);
 
 /* ---- simulation (simulate_dev.hpp): draws of (hidden path, observations) from the model the manager holds - the process whose
  * marginal likelihood the E-step computes.  A simulated contig has positions 1 .. N; position 0 is column 0 and carries no

@@ -364,6 +364,17 @@ class _PyInferenceManager:
         E.check(E.lib().smcpp_score_windows(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
         return out
 
+    def score_windows_exact(self, c=0, window=10_000):
+        """`[nder, ceil(P_L / window)]`: the score of contig `c` per window like `score_windows`, but exact on rows that a window
+        boundary cuts: every window gets the score of the positions that lie in it (position p >= 1 in window `(p - 1) // window`),
+        as if every row had been given as rows of span 1.  The vectors form only: SMCPP_SCORE_FORM=vectors (`_engine.set_option`),
+        at most 256 hidden states.  (include/smcpp_engine.h: smcpp_score_windows_exact.)"""
+        nw = C.c_longlong(0)
+        E.check(E.lib().smcpp_score_windows_exact(self._im, int(c), int(window), C.byref(nw), None))
+        out = np.empty((E.lib().smcpp_num_derivatives(self._im), nw.value))
+        E.check(E.lib().smcpp_score_windows_exact(self._im, int(c), int(window), C.byref(nw), E.dptr(out)))
+        return out
+
     def _hmm_tables(self):
         """(pi [M], T [M, M], E [K, M]) as plain float64 arrays, straight from the C getters."""
         K = E.lib().smcpp_num_keys(self._im)

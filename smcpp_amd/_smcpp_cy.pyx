@@ -126,6 +126,7 @@ cdef extern from "smcpp_engine.h":
     int smcpp_loglik_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
     int smcpp_score_rows(smcpp_im *im, int contig, long long start, long long stop, long long step, int parts, double *out) nogil
     int smcpp_score_windows(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
+    int smcpp_score_windows_exact(smcpp_im *im, int contig, long long window_bp, long long *n_windows, double *out) nogil
     int smcpp_simulate(smcpp_im *im, int n_contigs, const long long *lengths, int n_alpha, const int *alpha_keys, int quiet, unsigned long long seed, long long contig0, long long rep0, long long nreps, long long cap, const long long *resume_in, int *x0, long long *n_events, long long *pos, int *state, int *key, long long *resume_out) nogil
 # --- end generated ---
 
@@ -638,6 +639,20 @@ cdef class _PyInferenceManager:
         cdef double *op = &out[0]
         with nogil:
             rc = smcpp_score_windows(self._im, cc, W, &nw, op)
+        _check(rc)
+        return out[:nder * nw].reshape(nder, nw)
+
+    def score_windows_exact(self, c=0, window=10_000):
+        """`[nder, ceil(P_L / window)]`: `score_windows`, exact on rows that a window boundary cuts (every window gets the score of the
+        positions that lie in it).  The vectors form only: SMCPP_SCORE_FORM=vectors.  (include/smcpp_engine.h: smcpp_score_windows_exact.)"""
+        cdef int cc = c, rc
+        cdef long long W = window, nw = 0
+        _check(smcpp_score_windows_exact(self._im, cc, W, &nw, NULL))
+        cdef int nder = smcpp_num_derivatives(self._im)
+        cdef np.ndarray[double, ndim=1] out = np.empty(max(nder * nw, 1))
+        cdef double *op = &out[0]
+        with nogil:
+            rc = smcpp_score_windows_exact(self._im, cc, W, &nw, op)
         _check(rc)
         return out[:nder * nw].reshape(nder, nw)
 

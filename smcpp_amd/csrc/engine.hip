@@ -46,6 +46,7 @@
 #include "posterior_paths_dev.hpp"   // posterior paths: forward filtering, backward sampling (state / up / down per row, per position)
 #include "posterior_pos_dev.hpp"     // posterior positions: the marginal of single positions on a grid, its summaries, exact windows
 #include "loglik_track_dev.hpp"      // log-likelihood track: log c per caller's row, l(p) on a grid of positions, per window
+#include "score_seg_dev.hpp"         // ... and the score track's exact windows: the segments of rows a window boundary cuts (behind LlItem)
 #include "simulate_dev.hpp"          // simulation: (hidden path, observations) drawn from the model, event by event
 
 // The engine is one translation unit in eight parts (each part sees everything above it):

@@ -627,6 +627,10 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         // ... and of the last score track call: the engine rows it walked, its wavefronts and where a block's vectors are parked
         s += ", \"score_items\": " + std::to_string(im->sc_items) + ", \"score_waves\": " + std::to_string(im->sc_waves);
         s += std::string(", \"score_park\": \"") + (im->sc_vectors ? "global" : "lds") + "\", \"score_form\": \"" + (im->sc_vectors ? "vectors" : "matrix") + "\"";
+        // ... and of the last exact score windows call: the engine rows a window boundary cut, their segments and the wavefronts of
+        // the segment walk (0: no row was cut and it was not launched)
+        s += ", \"score_exact_items\": " + std::to_string(im->sx_nitems) + ", \"score_exact_segments\": " + std::to_string(im->sx_nseg);
+        s += ", \"score_exact_waves\": " + std::to_string(im->sx_waves);
     }
     s += "}";
     if (buf && cap > 0) {

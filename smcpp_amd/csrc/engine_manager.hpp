@@ -378,6 +378,8 @@ struct smcpp_im {
     const long long *ll_epos_dev(int c);          // EP [Le + 1] on the device
     const double *ll_prefix(int c);               // pre [Le + 1] on the device, on `stream`
     void ll_table(int c, long long pos0, long long pos1, long long step, bool windows);   // -> ll_items, ll_nslots (host)
+    void walk_item_table(int c, long long pos0, long long pos1, long long step, bool windows, std::vector<LlItem> &items,
+                         long long &nslots) const;                                        // the builder behind it: -> the caller's table
     void ll_walk(int c, long long step, double *slots);                                   // k_ll_walk over ll_items (not empty)
     // score track (score_track_dev.hpp, smcpp_score_rows / _windows): buffers of its own - the posterior products' and the loglik
     // track's are neither read nor written.  The tables G_pi | dT | G_E of the last E-step's parameters (built from the host Jacobians
@@ -400,6 +402,17 @@ struct smcpp_im {
     void score_tables_vec();                      // -> d_sv_tab (keeps E_on_dev as score_tables does)
     void score_rows_vec(int c, int nck);          // k_score_rows_vec -> d_sc_eng, on `stream`
     void score_rows_matrix(int c, int nck);       // k_score_rows -> d_sc_eng, on `stream`
+    // ... and its EXACT windows (score_seg_dev.hpp, smcpp_score_windows_exact; the vectors form only): the table of the engine rows a
+    // window boundary cuts - the loglik track's builder, a table, slots and outputs of its own (ll_items and the d_ll_* buffers are
+    // neither read nor written) -, the parts per segment of a cut row, the windows.  The parked blocks and checkpoints are the row
+    // walk's (d_sv_park, d_sc_ckpt: the segment walk runs behind it on `stream`)
+    std::vector<LlItem> sx_items;
+    long long sx_nslots = 0;                      // the segments of the last table: nq + 1 per item
+    DevBuf<LlItem> d_sx_items;
+    DevBuf<double> d_sx_seg, d_sx_out;
+    long long sx_nitems = 0, sx_nseg = 0;         // the items and segments of the last exact call (smcpp_describe)
+    int sx_waves = 0;                             // the wavefronts of its segment walk (0: it was not launched)
+    void score_segments_vec(int c, int nck, long long W, long long nw);   // k_score_segments_vec over sx_items (not empty) -> d_sx_seg
     bool ss_generators_only();            // the generators of T into ss_gen / ss_c0 (no underflow bound: the walks rescale every step)
     DevBuf<float> d_gpark;                 // k_gamma_rows_scan: [wavefronts][max span][64 NPL] parked forward vectors
     SsArgs ss_args;

@@ -824,10 +824,12 @@ const double *smcpp_im::ll_prefix(int c) {
 
 // The item table: the engine rows with a query position STRICTLY inside, ascending.  Grid: the queries are pos0, pos0 + step, ..
 // < pos1 and query j owns slot j; windows: the queries are the boundaries step, 2 step, .. < N and the slots are counted.
-void smcpp_im::ll_table(int c, long long pos0, long long pos1, long long step, bool windows) {
+// The builder is shared with the score track's exact windows, which keep a table of their own (`items`, `nslots`: the caller's).
+void smcpp_im::walk_item_table(int c, long long pos0, long long pos1, long long step, bool windows, std::vector<LlItem> &items,
+                               long long &nslots) const {
     const int Le = Ls[c];
-    ll_items.clear();
-    ll_nslots = 0;
+    items.clear();
+    nslots = 0;
     long long q0 = 0;
     for (int i = 1; i <= Le; ++i) {
         const RowInfo &ri = rowinfo[(size_t)contig_base[c] + i];
@@ -840,12 +842,15 @@ void smcpp_im::ll_table(int c, long long pos0, long long pos1, long long step, b
             if (g < end && g < pos1) {
                 const long long last = std::min(end - 1, pos1 - 1);
                 const int nq = (int)((last - g) / step + 1);
-                ll_items.push_back(LlItem{q0, g, windows ? ll_nslots : (g - pos0) / step, i, nq});
-                ll_nslots += nq;
+                items.push_back(LlItem{q0, g, windows ? nslots : (g - pos0) / step, i, nq});
+                nslots += nq;
             }
         }
         q0 = end;
     }
+}
+void smcpp_im::ll_table(int c, long long pos0, long long pos1, long long step, bool windows) {
+    walk_item_table(c, pos0, pos1, step, windows, ll_items, ll_nslots);
 }
 
 void smcpp_im::ll_walk(int c, long long step, double *slots) {
@@ -1175,6 +1180,82 @@ int smcpp_score_windows(smcpp_im *im, int c, long long window_bp, long long *n_w
                            im->d_sc_out.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(out, im->d_sc_out.p, sizeof(double) * (size_t)im->nder * nwin, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    API_END
+}
+
+// k_score_segments_vec over sx_items -> d_sx_seg [3][nder][sx_nslots], on `stream`, behind the row walk of the same call (whose
+// tables, parked blocks and checkpoints it takes over: one stream, one kernel after the other).  nw: the wavefronts, sized by the caller.
+void smcpp_im::score_segments_vec(int c, int nck, long long W, long long nw) {
+    const size_t nd = (size_t)nder, MS = (size_t)64 * NPL;
+    const SsArgs sa = walk_generators();
+    SgArgs g = SgArgs();
+    SvArgs &a = g.v;
+    a.M = M; a.Mp = Mp; a.L = Ls[c]; a.nck = nck; a.nder = nder; a.base = contig_base[c];
+    d_sv_park.alloc((size_t)nw * SV_BLK * 4 * MS);
+    d_sc_ckpt.alloc(std::max<size_t>(1, (size_t)nw * nck * MS));
+    d_sx_items.upload(sx_items, stream);               // (a member: it outlives the copy)
+    d_sx_seg.alloc((size_t)3 * nd * (size_t)sx_nslots);
+    a.rowinfo = d_rowinfo.p; a.g_span = d_g_span.p; a.E = d_E.p; a.alpha = d_alpha.p; a.beta = d_beta.p;
+    a.gamma0 = d_gamma0.p + (size_t)c * Mp;
+    a.Gpi = d_sv_tab.p; a.planes = a.Gpi + nd * MS; a.GE = a.planes + nd * 4 * MS;
+    a.park = d_sv_park.p; a.ckpt = d_sc_ckpt.p; a.out = nullptr;
+    g.nitems = (int)sx_items.size(); g.items = d_sx_items.p; g.W = W; g.nslots = sx_nslots; g.seg = d_sx_seg.p;
+    const dim3 grid((unsigned)ceil_div(nw, 4)), block(256);
+    for_npl(NPL, [&](auto x) {
+        constexpr int npl = decltype(x)::value;
+        if constexpr (npl <= 4) hipLaunchKernelGGL((k_score_segments_vec<npl>), grid, block, 0, stream, sa, g, (int)nw);   // (score_check: NPL <= 4)
+    });
+    HIPCHK(hipGetLastError());
+}
+
+int smcpp_score_windows_exact(smcpp_im *im, int c, long long window_bp, long long *n_windows, double *out) {
+    API_BEGIN
+    // the segment walk exists in the vectors form only (a matrix-form one would contract M x M per segment): asked first, so that the
+    // refusal names the switch whatever else the matrix form would object to
+    if (!im->score_form_vectors())
+        throw std::runtime_error("score track: exact windows exist in the vectors form of the row walk only: set SMCPP_SCORE_FORM=vectors "
+                                 "(one-population models prepared on the device, at most 256 hidden states)");
+    const int nck = im->score_check(c);
+    const long long nwin = window_count(im, c, window_bp, "score track", n_windows);
+    score_cap(im->nder, nwin, "the windows");
+    // the engine rows a boundary W, 2 W, .. < N cuts strictly inside; an item with nq boundaries owns nq + 1 slots
+    const long long N = im->user_prefix[c][im->user_Ls[c]];
+    im->walk_item_table(c, 0, N, window_bp, true, im->sx_items, im->sx_nslots);
+    for (size_t k = 0; k < im->sx_items.size(); ++k) im->sx_items[k].seg += (long long)k;
+    im->sx_nslots += (long long)im->sx_items.size();
+    const long long nitems = (long long)im->sx_items.size(), nslots = im->sx_nslots;
+    score_cap(3LL * im->nder, nslots, "the segments of the rows a window boundary cuts");
+    // scratch: the parts per engine row and per segment + the parked block and the checkpoints of one wavefront at the least
+    const size_t nd = (size_t)im->nder, MS = (size_t)64 * im->NPL;
+    const size_t fixed = (size_t)3 * nd * ((size_t)im->Ls[c] + 1 + (size_t)nslots) * sizeof(double);
+    const size_t per_wave = (size_t)SV_BLK * 4 * MS * sizeof(float) + (size_t)nck * MS * sizeof(double);
+    if (nitems > 0 && fixed + per_wave > (1ull << 30))
+        throw std::runtime_error("score track: the scratch of the exact windows (" + std::to_string(im->nder) + " directions x 3 parts x (" +
+                                 std::to_string(im->Ls[c] + 1) + " engine rows + " + std::to_string(nslots) +
+                                 " segments of cut rows)) exceeds the cap of 1 GiB: ask for a wider window");
+    if (!out) return 0;
+    im->score_rows(c, 0, 1, 1, 0, nck);                // every engine row -> d_sc_eng (the selection: column 0 alone, not used here)
+    hipStream_t s = im->stream;
+    long long nw = 0;
+    if (nitems > 0) {
+        nw = walk_waves(nitems, im->walk_slots(), per_wave, (1ull << 30) - fixed);
+        if (opt().has(smcpp_opt::O_SCORE_WAVES)) nw = std::min(nw, std::max<long long>(1, opt().ll(smcpp_opt::O_SCORE_WAVES, 1)));
+        im->score_segments_vec(c, nck, window_bp, nw);
+    } else {
+        im->d_sx_items.alloc(1);
+        im->d_sx_seg.alloc(1);
+    }
+    im->sx_nitems = nitems; im->sx_nseg = nslots; im->sx_waves = (int)nw;
+    if (nwin > 0) {                                    // (a contig without rows has no base pairs and no windows)
+        const long long *EP = im->ll_epos_dev(c);
+        im->d_sx_out.alloc((size_t)im->nder * nwin);
+        hipLaunchKernelGGL(k_score_windows_exact, dim3((unsigned)ceil_div(nwin, 4)), dim3(256), 0, s, (long long)im->Ls[c], window_bp, nwin,
+                           im->nder, EP, (const double *)im->d_sc_eng.p, (const LlItem *)im->d_sx_items.p, (int)nitems, nslots,
+                           (const double *)im->d_sx_seg.p, im->d_sx_out.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, im->d_sx_out.p, sizeof(double) * (size_t)im->nder * nwin, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(hipStreamSynchronize(s));
     API_END

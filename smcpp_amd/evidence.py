@@ -59,7 +59,7 @@ def compare_tracks(track_a, track_b, block=1):
 
 
 def score_track(model, contigs, M, n, theta, rho, window, alpha=1.0, polarization_error=0.5, a=None, device=-1, return_manager=False,
-                seeds=None, form=None):
+                seeds=None, form=None, exact=False):
     """The score of every contig under `model`, per window of `window` base pairs: d loglik / d direction, window by window
     (`im.score_windows`, include/smcpp_engine.h: smcpp_score_windows).  Built like `loglik_track` - `M` the number of hidden states
     (at most 64; at most 256 with `form="vectors"`) or their break points, one manager, the missing row in front of every contig - but on ONE `save_gamma` E-step, and
@@ -70,9 +70,15 @@ def score_track(model, contigs, M, n, theta, rho, window, alpha=1.0, polarizatio
     inference manager.  `form`: "matrix" or "vectors", the form of the engine's row walk (SMCPP_SCORE_FORM, set around this
     function's own score calls and put back afterwards; None: whatever the environment says, the matrix form when it says nothing).
     The vectors form serves one-population models up to 256 hidden states; a manager that is kept answers later calls in the form
-    the switch names then."""
+    the switch names then.  `exact=True`: `im.score_windows_exact` instead - a row that a window boundary cuts gives every window
+    the score of the positions that lie in it, not an even share (what un-binned data need, where one row spans many windows).  It
+    exists in the vectors form only: `form=None` then means "vectors", and `form="matrix"` is refused."""
     if form not in (None, "matrix", "vectors"):
         raise ValueError(f"score_track: form {form!r} (expected None, 'matrix' or 'vectors')")
+    if exact and form == "matrix":
+        raise ValueError("score_track: exact windows exist in the vectors form only (form='vectors', or leave form unset)")
+    if exact and form is None:
+        form = "vectors"
     hidden_states = None if np.isscalar(M) else np.asarray(M, dtype=float)
     nstates = int(M) if hidden_states is None else len(hidden_states) - 1
     if seeds is not None:
@@ -87,15 +93,16 @@ def score_track(model, contigs, M, n, theta, rho, window, alpha=1.0, polarizatio
         model.derivative_seeds = lambda: seeds
     hs, obs, im = _decode_setup(model, contigs, nstates, n, theta, rho, alpha, polarization_error, hidden_states, device, a, None, None, 1,
                                 save_gamma=True)
+    windows = (lambda c: im.score_windows_exact(c, int(window))) if exact else (lambda c: im.score_windows(c, int(window)))
     if form is None:
-        track = [im.score_windows(c, int(window)) for c in range(len(obs))]
+        track = [windows(c) for c in range(len(obs))]
     else:
         import os
         from . import _engine
         before = os.environ.get("SMCPP_SCORE_FORM")
         _engine.set_option("SMCPP_SCORE_FORM", form)
         try:
-            track = [im.score_windows(c, int(window)) for c in range(len(obs))]
+            track = [windows(c) for c in range(len(obs))]
         finally:
             _engine.set_option("SMCPP_SCORE_FORM", before)
     if return_manager:

@@ -10,12 +10,15 @@ Three inputs, one manager each, in one process, the model differentiable in ever
 
 Per input: two `save_gamma` E-steps to settle, then `--repeats` rounds after `--warmup` of (a) the E-step (with its 16-direction
 preparation), wall clock up to the log-likelihood on the host, (b) `posterior_transitions(0)`, and per form (SMCPP_SCORE_FORM set
-through `_engine.set_option` around the leg) (c) `score_rows(0)`, (d) `score_rows(0, parts=True)`, (e) `score_windows(0, W)`; every
-call ends in a device synchronise and a copy to the host.  The forms alternate inside every round, so they see the same machine.  The
+through `_engine.set_option` around the leg) (c) `score_rows(0)`, (d) `score_rows(0, parts=True)`, (e) `score_windows(0, W)`, in
+the vectors form also (f) `score_windows_exact(0, W)` - the windows exact on rows a boundary cuts - and, at M <= 64, its neighbours
+`posterior_windows_exact(0, W)` and `loglik_windows(0, W)` as yardsticks; every call ends in a device synchronise and a copy to the
+host.  The forms alternate inside every round, so they see the same machine.  The
 first score call of a form behind an E-step also builds and uploads its tables; it is timed apart as `first_call_ms`.  Reported per
 leg: the minimum, the median and the spread (max - min); per form the launch shape (`score_items`, `score_waves`, `score_park`; read
 once, outside the timed rounds), the ratios of (c) to (b), to (a) and to the matrix form's (c) of the same run, and how far the
-score's sum lies from Q's gradient.  One JSON line per input, to stdout and appended to --out.
+score's sum lies from Q's gradient; for the exact windows the rows a boundary cut (`score_exact_items`), their segments and the
+wavefronts of the segment walk (0: it was not launched), and the ratio of (f) to (e) of the same run.  One JSON line per input, to stdout and appended to --out.
 
     python tools/score_track_probe.py [--rows N] [--repeats K] [--warmup W] [--window BP] [--only NAME] [--out FILE]
 """
@@ -91,6 +94,10 @@ def main():
             legs[form + ":score_rows"] = in_form(form, lambda: im.score_rows(0))
             legs[form + ":score_rows_parts"] = in_form(form, lambda: im.score_rows(0, parts=True))
             legs[form + ":score_windows"] = in_form(form, lambda: im.score_windows(0, args.window))
+        legs["vectors:score_windows_exact"] = in_form("vectors", lambda: im.score_windows_exact(0, args.window))
+        if M <= 64:
+            legs["posterior_windows_exact"] = lambda: im.posterior_windows_exact(0, args.window)
+            legs["loglik_windows"] = lambda: im.loglik_windows(0, args.window)
         times = {k: [] for k in legs}
         for r in range(args.warmup + args.repeats):
             for k, f in legs.items():
@@ -121,6 +128,13 @@ def main():
                 "score_rows_over_estep": round(best[form + ":score_rows"] / best["estep_save_gamma"], 3),
                 "score_rows_over_matrix_form": round(best[form + ":score_rows"] / best["matrix:score_rows"], 3) if "matrix" in forms else None,
                 "parts_sum_off_q_jacobian_rel": float(np.max(np.abs(rows.sum(axis=2) - want) / np.maximum(np.abs(rows).sum(axis=2), 1e-300)))}
+        exact = in_form("vectors", lambda: im.score_windows_exact(0, args.window))()
+        d = im.describe()
+        plain = in_form("vectors", lambda: im.score_windows(0, args.window))()
+        per_form["vectors"]["exact_windows"] = {
+            "score_exact_items": d["score_exact_items"], "score_exact_segments": d["score_exact_segments"], "score_exact_waves": d["score_exact_waves"],
+            "exact_over_score_windows": round(best["vectors:score_windows_exact"] / best["vectors:score_windows"], 3),
+            "max_abs_exact_minus_apportioned": float(np.max(np.abs(exact - plain))), "max_abs_window": float(np.max(np.abs(exact)))}
         plan = d["plan"]
         res = {"input": name, "M": M, "directions": int(rows.shape[1]), "rows": len(contig), "positions": int(contig[:, 0].astype(np.int64).sum()),
                "longest_row": int(contig[:, 0].max()), "window": args.window, "repeats": args.repeats,

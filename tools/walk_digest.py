@@ -2,7 +2,7 @@
 compute the same bits.
 
 The row walks of the posterior transitions, the sampled paths, the per-position posteriors, the log-likelihood track and the score
-track (smcpp_amd/csrc/*_dev.hpp over walk_dev.hpp) are run on small seeded inputs: three ragged contigs of a few hundred un-binned
+track with its exact windows (smcpp_amd/csrc/*_dev.hpp over walk_dev.hpp) are run on small seeded inputs: three ragged contigs of a few hundred un-binned
 rows with spans 1, 2, 63, 64, 65, 128, 129 and 200 placed by hand (rows of one, two and three blocks of 64 positions, and a last
 block of one position), at M = 5, 64, 65, 130, 200, 256, 300 and 520 hidden states (padding states; 1, 2, 3, 4, 8 and 16 states per
 lane).  SMCPP_SPLIT_SPANS=0 keeps the long rows un-cut beyond 64 states, so the checkpoint pass runs; beyond 256 states the engine
@@ -67,6 +67,8 @@ def products(np, im, c, w, set_option):
         def f():
             set_option("SMCPP_SCORE_FORM", form)
             try:
+                if what == "exact":
+                    return [im.score_windows_exact(c, W) for W in (WINDOW, 7, 1)]
                 return im.score_rows(c, parts=True) if what == "rows" else im.score_windows(c, WINDOW)
             finally:
                 set_option("SMCPP_SCORE_FORM", None)
@@ -89,6 +91,8 @@ def products(np, im, c, w, set_option):
         "score_windows_matrix": score("matrix", "windows"),
         "score_rows_vectors": score("vectors", "rows"),
         "score_windows_vectors": score("vectors", "windows"),
+        # (behind every earlier line, so that those run in the order they always ran in)
+        "score_windows_exact_vectors": score("vectors", "exact"),
     }
 
 
