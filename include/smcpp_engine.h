@@ -217,7 +217,11 @@ int smcpp_debug_chunks(smcpp_im *im, int backward, int cap, int *out);
  * table of them); smcpp_reload_options re-reads the environment (tests; never while an E-step runs).  smcpp_describe writes one
  * JSON object - the switches that are set and the plan `im` resolved (chain family, chunk counts, history passes, whether the
  * stored passes of the last E-step ran their scans in float; "q_route": whether the last smcpp_q was evaluated by the device
- * kernels, "device", by the host loops, "host", or not yet, "none") - and returns the length it needs; `im` may be NULL. */
+ * kernels, "device", by the host loops, "host", or not yet, "none"; "estep_redone": 1 when the last E-step ran twice - the scan
+ * chains' attempt on a device-prepared emission table was abandoned because an entry is too small for `span` scan steps, and the
+ * E-step redone on the dense kernels -, "estep_redone_why": the reason, "" otherwise; "estep_chain_family": the chain family the
+ * last E-step ended on, -1 before the first; "scan_chains_refused": "", "transition structure" or "emission underflow", why a
+ * manager planned for the scan chains ran its last E-step on the dense kernels) - and returns the length it needs; `im` may be NULL. */
 void smcpp_reload_options(void);
 int smcpp_describe(smcpp_im *im, char *buf, int cap);
 /* Test hook of family 5: one position of both scan chains on nvec vectors: out_f = e o (T^T x), out_b = T (e o x); T is

@@ -160,8 +160,10 @@ struct DevPrep {
     size_t in_cap = 0;
     DevBuf<double> d_tab, d_sfs_v, d_sfs_d, d_Eg_v, d_Eg_d, d_El, d_Es;
     std::vector<double> e_tab, e_sfs_v, e_sfs_d, e_Eg_v, e_Eg_d;     // emulate
-    int *h_flags = nullptr, *d_flags_view = nullptr;
+    int *h_flags = nullptr, *d_flags_view = nullptr;      // host-mapped: [0, 16) the flag words, [16, 16 + Kk) PrepOut::key_ok
+    int flags_cap = 0;
     int e_flags[4] = {0, 0, 0, 0};
+    std::vector<int> e_keyok;
     int last_nder = 0;
     hipEvent_t ev_done = nullptr;        // recorded behind the last preparation's kernels: the staging block and the flag words
     bool in_flight = false;              // are rewritten only after it has completed
@@ -215,9 +217,15 @@ struct DevPrep {
             HIPCHK(hipMemset(d_El.p, 0, d_El.n * sizeof(double)));
             HIPCHK(hipMemset(d_Es.p, 0, d_Es.n * sizeof(double)));
             d_sfs_v.alloc((size_t)M * 3 * (n + 1));
-            if (!h_flags) {
-                HIPCHK(hipHostMalloc((void **)&h_flags, 64, hipHostMallocCoherent | hipHostMallocMapped));
+            if (flags_cap < 16 + Kk) {
+                if (in_flight) { HIPCHK(hipEventSynchronize(ev_done)); in_flight = false; }      // (a preparation may still raise flags)
+                if (h_flags) (void)hipHostFree(h_flags);
+                h_flags = nullptr; d_flags_view = nullptr; flags_cap = 0;
+                const int cap = 16 + Kk + 64;
+                HIPCHK(hipHostMalloc((void **)&h_flags, sizeof(int) * cap, hipHostMallocCoherent | hipHostMallocMapped));
                 HIPCHK(hipHostGetDevicePointer((void **)&d_flags_view, h_flags, 0));
+                std::memset(h_flags, 0, sizeof(int) * cap);
+                flags_cap = cap;                  // (only now: a failed allocation leaves the next set_keys to try again)
             }
         } else {
             e_Eg_v.assign((size_t)Kk * M, 0.0);
@@ -296,6 +304,8 @@ struct DevPrep {
             po.sfs_v = e_sfs_v.data(); po.sfs_d = nder ? e_sfs_d.data() : nullptr; po.Eg_v = e_Eg_v.data(); po.Eg_d = nder ? e_Eg_d.data() : nullptr;
             e_flags[0] = e_flags[1] = e_flags[2] = 0;
             po.flags = e_flags;
+            e_keyok.assign(std::max(1, Kk), 0);
+            po.key_ok = e_keyok.data();
             if (nder) {
                 smcpp_dev::Tables<SD> tb;
                 tb.carve(reinterpret_cast<SD *>(e_tab.data()), n, K, ng);
@@ -315,6 +325,8 @@ struct DevPrep {
         po.El_v = d_El.p; po.Es_v = MS > 0 ? d_Es.p : nullptr;
         h_flags[0] = h_flags[1] = h_flags[2] = 0;
         po.flags = d_flags_view;
+        std::memset(h_flags + 16, 0, sizeof(int) * Kk);
+        po.key_ok = d_flags_view + 16;
         HIPCHK(hipMemcpyAsync(d_in, hb, bytes, hipMemcpyHostToDevice, s));
         const int pairs = (n + 1) * n;
         const int nt = std::min(512, std::max(64 * ceil_div(3 * n + 2, 64), 64 * ceil_div(pairs, 64)));
@@ -353,6 +365,15 @@ struct DevPrep {
         in_flight = true;
     }
     const int *flags() const { return emulate ? e_flags : h_flags; }
+    // The table of the last preparation fails a bound of the scan chains on a row they would expand step by step (prep_dev.hpp:
+    // SS_SPAN_LOG_MIN, flag 2; SS_SPAN_LOG_MAX, a key with such a row and no entry that passes).  After the stream has drained.
+    bool span_underflow() const {
+        if (flags()[2]) return true;
+        const int *ok = emulate ? e_keyok.data() : h_flags + 16;
+        for (int k = 0; k < Kk; ++k)
+            if (h_si[off_maxspan + k] > 1 && !ok[k]) return true;
+        return false;
+    }
     // Results to the host (after the stream has drained): E [Kk][M], dE [Kk*M][nder], sfs [M][C], dsfs [M*C][nder]
     // (with_sfs = false: the emission table and its Jacobian alone; sfs / dsfs are left as they are)
     void fetch(std::vector<double> &Ev, std::vector<double> &dEv, std::vector<double> &sfs, std::vector<double> &dsfs, bool with_sfs = true) {

@@ -611,6 +611,13 @@ int smcpp_describe(smcpp_im *im, char *buf, int cap) {
         static const char *const route[] = {"none", "device", "host"};
         s += std::string(", \"q_route\": \"") + route[im->q_route] + "\"";
         s += describe_param_plan(im);
+        // the last E-step: did it run twice (the scan chains' attempt on a device-prepared table abandoned for DevPrep flag 2, then the
+        // dense kernels) and why; the chain family it ended on (the plan's, or the plan's dense fallback; -1: no E-step yet); why a
+        // manager planned for the scan chains fell back ("": it did not)
+        s += std::string(", \"estep_redone\": ") + (im->estep_redone ? "1" : "0") + ", \"estep_redone_why\": \"" + im->estep_redone_why + "\"";
+        s += ", \"estep_chain_family\": " + std::to_string(!im->estep_done ? -1 : im->estep_route.ss_active ? chain_family(im->plan) : (int)im->plan.dense);
+        s += std::string(", \"scan_chains_refused\": \"") + (!im->estep_done || !im->plan.scan || im->estep_route.ss_active ? ""
+                 : im->ss_underflow ? "emission underflow" : "transition structure") + "\"";
         // the launch shape of the last posterior path call - paths per wavefront, batches, wavefronts - and the wavefronts of the
         // last posterior transition call (0: none yet); a wavefront takes more than one batch / row where there are fewer of them
         s += ", \"path_batch\": " + std::to_string(im->pp_batch) + ", \"path_batches\": " + std::to_string(im->pp_batches);

@@ -171,7 +171,7 @@ struct smcpp_im {
     double theta = NAN, rho = NAN, alpha = 1.0;
     bool have_raw = false, dirty = true, params_fresh = false;
     // a setter: the prepared tables go; results_stale: so do the last E-step's vectors; model_setter: a manager with a model leaves the raw path
-    void params_changed(bool model_setter, bool results_stale = true) { params_fresh = false; dirty = dirty || results_stale; have_raw = have_raw && !(model_setter && have_model); }
+    void params_changed(bool model_setter, bool results_stale = true) { params_fresh = false; ss_range_refused = false; dirty = dirty || results_stale; have_raw = have_raw && !(model_setter && have_model); }
     std::vector<double> pi, T, E;          // [M], [M*M], [K*M]
     smcpp_host::ModelParams model;         // a, s (for set_params); the distinguished model of a two-population manager
     smcpp_host::ModelParams model_p1, model_p2;          // two populations: per-population pieces (set_params_twopop)
@@ -223,7 +223,7 @@ struct smcpp_im {
     bool E_on_dev = false, force_host_prep = false;
     ParamPlan param_plan; EstepRoute estep_route;         // of the last prepare_params() / set_raw; of the last E-step (smcpp_describe: "parameters")
     ParamPlan resolve_param_plan() const;
-    EstepRoute resolve_estep_route(bool structured_T) const;
+    EstepRoute resolve_estep_route(bool structured_T, bool underflow = false) const;     // underflow: why the scan chains are refused (ss_underflow)
     void dev_prepare(const std::vector<int> &pk, int Kp_);     // (the prepared key list: global or this rank's)
     void sync_host_E();
     void fetch_prepared_table(std::vector<double> &E_out, std::vector<double> &dE_out, bool whole);     // the device's table -> host (whole: + emission, Eg / dEg)
@@ -423,12 +423,21 @@ struct smcpp_im {
     void update_pi_default();
     bool debug = false;                    // InferenceManager::debug (_smcpp.pxd:53): declared by the reference, read by nothing
     void upload_chunk_state();
-    bool ss_extract_generators();          // generators of T (verified entry by entry) into ss_gen; false: T has no such structure
+    bool ss_extract_generators();          // generators of T (verified entry by entry) into ss_gen; false: T has no such structure,
+                                           // or (ss_underflow) an emission entry of a host table is too small for `span` scan steps
+    bool ss_underflow = false;
+    // the scan chains ran on these parameters and a row's evidence left the range of their float intermediates (kernels.hpp:
+    // LoglikArgs::range_flag, read by estep()): until the parameters change, ss_extract_generators refuses them like a bound
+    bool ss_range_refused = false;
+    // the last E-step ran twice: the scan chains' attempt on a device-prepared table was abandoned (DevPrep flag 2) and the E-step
+    // redone on the dense kernels (smcpp_describe: "estep_redone", "estep_redone_why")
+    bool estep_redone = false;
+    const char *estep_redone_why = "";
     std::vector<double> ss_gen;            // [10][MS]: f_dc f_g f_cg f_b f_a f_d b_dc b_g b_b b_a
     double ss_c0 = 0.0;
     void ss_launch_initial();
     void ss_launch_passes(int upto);
-    void run_chains_ss();
+    bool run_chains_ss();                  // false: not converged on a device table that DevPrep flag 2 names (estep redoes it)
     int hot_eig = -1, hot_eig2 = -1;
     // eigen-free pre-pass (chains2.hpp: k_group_powers, POWER instantiations): pass 0 runs on group powers while the host
     // solves the eigenproblems; only for short, few spans (binned data) and chunks short enough that pass 1 re-runs them whole
@@ -560,7 +569,7 @@ struct smcpp_im {
     AccArgs acc_args(const HostDev<Slab> &sl, const int *perm, const int2 *permk, double *part, double *gpart);
     void launch_span_gt1_rank(const StatsPlan &p), launch_span1_branch(const StatsPlan &p), launch_gamma_rows(const StatsPlan &p);
     void launch_span_gt1_branch(const StatsPlan &p, FinArgs &fa);
-    void estep();
+    void estep(bool redo = false);         // redo: estep()'s own second entry (the redo above)
     void fetch_stats();
     void prepare_params();
 };

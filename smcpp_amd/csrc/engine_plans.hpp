@@ -500,14 +500,18 @@ bool smcpp_im::ss_generators_only() {
 }
 
 bool smcpp_im::ss_extract_generators() {
+    ss_underflow = false;
     if (!ss_generators_only()) return false;
+    if (ss_range_refused) { ss_underflow = true; return false; }
     // a row of span s applies its operator s times without rescaling: keep clear of underflow
-    // (a device-prepared table is checked by the kernel that forms it: DevPrep flag 2, looked at when the E-step has drained)
+    // (a device-prepared table is checked by the kernel that forms it: DevPrep flag 2, looked at when the chains have drained)
     if (!E_on_dev) for (const Group &gr : groups) {
         if (plan.hybrid && gr.span > plan.hyb_th) continue;          // an eigen-power step, not `span` scan steps
-        double mn = 1.0;
-        for (int i = 0; i < M; ++i) mn = std::min(mn, E[(size_t)gr.kid * M + i]);
-        if (!(mn > 0.0) || (double)gr.span * std::log(mn) < -450.0) return false;
+        double mn = 1.0, mx = 0.0;
+        for (int i = 0; i < M; ++i) { mn = std::min(mn, E[(size_t)gr.kid * M + i]); mx = std::max(mx, E[(size_t)gr.kid * M + i]); }
+        // (prep_dev.hpp has the two bounds and where they come from)
+        if (!(mn > 0.0) || (double)gr.span * std::log(mn) < smcpp_dev::SS_SPAN_LOG_MIN ||
+            (gr.span > 1 && (double)gr.span * std::log(mx) < smcpp_dev::SS_SPAN_LOG_MAX)) { ss_underflow = true; return false; }
     }
     return true;
 }
@@ -720,7 +724,9 @@ bool smcpp_im::wait_done(int epoch) {
     return true;
 }
 
-void smcpp_im::run_chains_ss() {
+// false: no pass was quiet AND the device preparation flagged its emission table (DevPrep flag 2: the vectors of a long row may have
+// underflowed to zero, then 0 x inf) - the caller redoes the E-step on the dense kernels; without the flag that is an error.
+bool smcpp_im::run_chains_ss() {
     hipStream_t s = stream;
     const int *chf = h_flags, *chb = h_flags + (plan.max_pass + 1);
     const int p0 = chain_pass.pass0;
@@ -770,7 +776,12 @@ void smcpp_im::run_chains_ss() {
         fprintf(stderr, "[cycles] ss pass 0, chunk 1: forward %lld shader clocks, %lld x 10 ns, %lld positions, %lld rows; backward %lld "
                 "clocks, %lld x 10 ns, %lld positions, %lld rows\n", h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]);
     }
-    if (q < 0) { stats_enqueued = false; throw std::runtime_error("chunk-boundary iteration did not converge"); }
+    if (q < 0) {
+        stats_enqueued = false;
+        // (the preparation kernel precedes the chains on the stream, its flag words sit in host-mapped memory, and the queue has drained)
+        if (E_on_dev && dprep && dprep->span_underflow()) return false;
+        throw std::runtime_error("chunk-boundary iteration did not converge");
+    }
     // the flags of the first round did not certify, yet the very next pass was quiet: on this input the last working pass rewrites
     // end vectors WITHIN the tolerance - from now on the all-skip pass is launched up front again (one round instead of two)
     if (first_launched >= 0 && q == first_launched) ss_need_cert_pass = true;
@@ -779,6 +790,7 @@ void smcpp_im::run_chains_ss() {
     // every launched pass carried the end vectors forward (a skipped chunk copies them): they sit at the last pass's parity
     ss_warm_parity = (ss_launched - 1) & 1;
     ss_warm_valid = true;
+    return true;
 }
 
 void smcpp_im::run_stats() {
@@ -1184,6 +1196,11 @@ bool smcpp_im::enqueue_stats(int signal_epoch) {
     la.contig_base = d_contig_base.p; la.contig_L = d_contig_L.p; la.partial = d_llpart.p; la.loglik = d_loglik.p;
     la.logc = d_logc.p; la.nblk = lay.llblk;
     la.loglik_host = d_ll_view;          // the final kernel writes the per-contig values into the pinned array as well: no copy
+    if (estep_route.ss_active && h_done) {
+        // (h_done[8]: beside the completion word, cleared here - nothing of an earlier E-step or round is in flight when the host enqueues)
+        h_done[8] = 0;
+        la.g_span = d_g_span.p; la.hyb_th = plan.hybrid ? plan.hyb_th : 0x7fffffff; la.range_flag = d_done_view + 8;
+    }
     if (p.loglik == StatsPlan::THIRD) fork_from_chains(sl);
     hipLaunchKernelGGL(k_loglik_partial, dim3(lay.llblk, n_contigs), dim3(256), 0, sl, la);
     hipLaunchKernelGGL(k_loglik_final, dim3(n_contigs), dim3(256), 0, sl, la);
@@ -1311,7 +1328,7 @@ void smcpp_im::resolve_timing() {
 }
 
 // structured_T: what ss_extract_generators() found; in front of it plan.scan, "not disproved yet" - then only the first refusal can fire.
-EstepRoute smcpp_im::resolve_estep_route(bool structured_T) const {
+EstepRoute smcpp_im::resolve_estep_route(bool structured_T, bool underflow) const {
     EstepRoute r;
     // span > 1 rows without an eigensystem (k_span_fold); with save_gamma their per-row posteriors come from scan steps too (k_gamma_rows_scan)
     r.eigfree_static = !opt().off(smcpp_opt::O_EIGFREE) && Mp <= 1024 && ss_max_span <= 64 && (!save_gamma || !opt().off(smcpp_opt::O_GAMMA_SCAN));
@@ -1320,6 +1337,10 @@ EstepRoute smcpp_im::resolve_estep_route(bool structured_T) const {
     if (Mp > 256 && !(plan.scan && r.eigfree_static))
         r.refuse = "more than 256 hidden states: only the scan chains with eigen-free statistics are built (rows longer than 64 positions are cut "
                    "into pieces at construction unless SMCPP_SPLIT_SPANS=0 / SMCPP_EIGFREE=0 forbid it or the pieces would not fit the device)";
+    else if (Mp > 256 && !r.ss_active && underflow)
+        r.refuse = "more than 256 hidden states: an emission entry is too small for the scan chains, which take a row of span s in s steps "
+                   "without rescaling (on a row of span s > 1, s x log(smallest entry of its key's emission vector) < -450 or s x log(largest "
+                   "entry) < -80; the transition matrix has the structure they need, and the dense fallback kernels stop at 256)";
     else if (Mp > 256 && !r.ss_active)
         r.refuse = "more than 256 hidden states: the transition matrix must have the structure of the reference's "
                    "HJTransition (the dense fallback kernels stop at 256)";
@@ -1328,9 +1349,10 @@ EstepRoute smcpp_im::resolve_estep_route(bool structured_T) const {
     return r;
 }
 
-void smcpp_im::estep() {
+void smcpp_im::estep(bool redo) {
     if (std::isnan(theta) || std::isnan(rho) || std::isnan(alpha))
         throw std::runtime_error("theta / rho / alpha must be set");
+    if (!redo) { estep_redone = false; estep_redone_why = ""; }
     HIPCHK(hipSetDevice(device));
     timing_pending = false;          // (intervals nobody asked for: the events are about to be recorded again)
     auto t0 = std::chrono::steady_clock::now();
@@ -1351,9 +1373,14 @@ void smcpp_im::estep() {
     HIPCHK(hipEventRecord(ev[EV_ESTEP], stream));
     EstepRoute er = resolve_estep_route(plan.scan);                  // in front of the generators: T may have the structure
     if (er.refuse) throw std::runtime_error(er.refuse); if (er.host_E) sync_host_E();
-    er = resolve_estep_route(plan.scan && ss_extract_generators());  // ... and with what they say about T
+    const bool structured = plan.scan && ss_extract_generators();     // ... and with what they say about T (and, of a host table, the bound)
+    er = resolve_estep_route(structured, plan.scan && ss_underflow);
     if (er.refuse) throw std::runtime_error(er.refuse); if (er.host_E) sync_host_E();       // (refused: estep_route stays the last E-step's)
     estep_route = er;
+    if (plan.scan && !er.ss_active && ss_underflow && g_logger_cb)
+        log_msg("WARNING", "E-step: the scan chains are refused on these parameters (%s): chain family %d instead of %d",
+                ss_range_refused ? "a row's evidence left the range of their float intermediates" : "an emission entry is too small for a row's span",
+                (int)plan.dense, plan.hybrid ? 6 : 5);
     tr.mark("estep: extract generators");
     prepass_launched = false;
     if (!estep_route.ss_active) { ss_warm_valid = false; stage_static_and_prepass(); }   // (when eligible) pass 0 of both chains starts now, on eigen-free operands
@@ -1363,19 +1390,37 @@ void smcpp_im::estep() {
     tr.mark("estep: host_prep_and_upload");
     if (estep_route.ss_active && plan.hybrid) ss_launch_initial();       // hybrid rows read the eigensystems: the chains start behind them
     auto t1 = std::chrono::steady_clock::now();
-    if (estep_route.ss_active) run_chains_ss(); else run_chains();
+    bool chains_ok = true;
+    if (estep_route.ss_active) chains_ok = run_chains_ss(); else run_chains();
     tr.mark("estep: chains (host view)");
-    run_stats();
+    if (chains_ok) run_stats();
     tr.mark("estep: statistics enqueued");
     if (E_on_dev) {
         dprep->check_flags();
-        if (estep_route.ss_active && dprep->flags()[2]) {
+        if (estep_route.ss_active && dprep->span_underflow()) {
             // an emission entry so small that `span` scan steps underflow (ss_extract_generators' bound, evaluated by the kernel
-            // that formed the table): this E-step is redone on the dense kernels from the host copy of the same parameters
+            // that formed the table): this E-step is redone on the dense kernels from the host copy of the same parameters - whether
+            // the chains' attempt converged on that table or not (run_chains_ss).  The second entry finds the table on the host, so
+            // the host bound sends it to the dense kernels (or, beyond 256 states, to the refusal that names the bound).
             sync_host_E();
-            estep();
+            estep_redone = true;
+            estep_redone_why = "device preparation: an emission entry is too small for `span` scan steps without rescaling (span x log(smallest entry) < -450 "
+                               "or span x log(largest entry) < -80)";
+            estep(true);
             return;
         }
+    }
+    if (estep_route.ss_active && h_done && h_done[8]) {
+        // the bounds are necessary, not sufficient - a row's evidence depends on the data: the log-likelihood kernel found a scanned
+        // row whose evidence left the range of the scan steps' float intermediates (kernels.hpp: LoglikArgs::range_flag), so what
+        // the chains and the statistics computed cannot be trusted.  Redone on the dense kernels; remembered until the parameters change.
+        sync_host_E();
+        ss_range_refused = true;
+        estep_redone = true;
+        estep_redone_why = "scan chains: the evidence of a row of span > 1 is too small for `span` scan steps without rescaling (|log c| > 80 "
+                           "or not finite)";
+        estep(true);
+        return;
     }
     auto t2 = std::chrono::steady_clock::now();
     // the event intervals are read when somebody asks for them (smcpp_last_timing, the debug log): EV_STATS_DONE sits BEHIND the

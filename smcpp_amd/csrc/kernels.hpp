@@ -680,7 +680,17 @@ struct LoglikArgs {
     double *loglik_host;          // optional: device view of a pinned host array that receives the same values (no copy afterwards)
     double *logc;                 // optional [rows]: log_c per row (needed by the span-1 weights)
     int nblk;
+    // The scan chains' guard on what they computed (null: none).  A row of span s that they expanded step by step (1 < s <= hyb_th)
+    // has its evidence c in cnorm un-scaled.  The scan steps carry FLOAT intermediates - every scan of the stored passes at one state
+    // per lane, the float running sum of the backward step in every form - and the span fold applies that step to rows scaled by
+    // 1 / c: FLT_MIN = e^-87.3, FLT_MAX = e^88.7, and a sum over up to 1024 states of entries up to 1 / c adds log 1024 = 6.9, so
+    // |log c| has to stay below 81.8.  A row outside SS_EVIDENCE_LOG_RANGE (or not finite) raises *range_flag (host-mapped, a
+    // plain store of 1): estep() redoes the E-step on the dense kernels.
+    const int *g_span = nullptr;  // [G]
+    int hyb_th = 0x7fffffff;
+    int *range_flag = nullptr;
 };
+constexpr double SS_EVIDENCE_LOG_RANGE = 80.0;
 
 __global__ __launch_bounds__(256) void k_loglik_partial(LoglikArgs a) {
     __shared__ double red[256];
@@ -694,6 +704,7 @@ __global__ __launch_bounds__(256) void k_loglik_partial(LoglikArgs a) {
     for (int ell = lo + threadIdx.x; ell <= hi; ell += 256) {
         const RowInfo ri = a.rowinfo[base + ell];
         double lc = log(a.cnorm[base + ell]);
+        if (a.range_flag && ri.gid >= 0 && a.g_span[ri.gid] <= a.hyb_th && !(fabs(lc) <= SS_EVIDENCE_LOG_RANGE)) *a.range_flag = 1;
         if (ri.gid >= 0) lc += a.g_logscale[ri.gid];
         a.logc[base + ell] = lc;
         s += lc;

@@ -118,7 +118,25 @@ struct PrepOut {
     // one word per condition (plain stores of 1, no read-modify-write): [0] an emission entry left (0, 1], [1] a conditioned
     // SFS is not a probability distribution, [2] an emission entry is so small that `span` scan steps would underflow
     int *flags = nullptr;
+    // [Kk], cleared by the host before the launch: 1 = some entry of the key's vector passes SS_SPAN_LOG_MAX on the key's longest
+    // scanned row (written for keys with such a row only); a key that stays 0 has NO such entry (DevPrep::span_underflow)
+    int *key_ok = nullptr;
 };
+// The scan chains take a row of span s in s steps WITHOUT rescaling (chains_ss.hpp), the eigen-free statistics fold the same steps.
+// Two bounds on s log(e_h) over the row's emission vector decide whether they may (here for a device table, ss_extract_generators
+// for a host table):
+//   SS_SPAN_LOG_MIN on the SMALLEST entry keeps every entry of an fp64 vector a normal number;
+//   SS_SPAN_LOG_MAX on the LARGEST entry: T is row-stochastic and the row starts from a vector that sums to one, so the row's
+//     evidence c (the sum after s steps) is at most max_h(e_h)^s.  The scan steps carry FLOAT intermediates - every scan of the
+//     stored passes at one state per lane (ss_x_scan_fwd / _bwd), the float running sum of the backward step in every form - and
+//     the span fold applies that step to rows scaled by 1 / c.  FLT_MIN = e^-87.3, FLT_MAX = e^88.7, and a sum over up to 1024
+//     states of entries up to 1 / c adds log 1024 = 6.9: |log c| has to stay below 81.8.  A row whose UPPER bound on c already
+//     misses that cannot be taken (measured: NaN log-likelihoods at one state per lane, NaN xi sums beyond 64 states -
+//     tests/test_gpu_underflow.py).  This bound only spares the scan attempt where it cannot succeed: c itself depends on the data
+//     (2 to 14 below the upper bound in log on the test contigs), so every E-step on the scan chains ALSO checks the evidence it
+//     computed for each such row (kernels.hpp: LoglikArgs::range_flag, SS_EVIDENCE_LOG_RANGE) and is redone on the dense kernels
+//     when one left the range.
+constexpr double SS_SPAN_LOG_MIN = -450.0, SS_SPAN_LOG_MAX = -80.0;
 // Tables of k_prep_tables, per direction GROUP g (a group = the directions one scalar carries; one group for plain doubles), piece-
 // major so that the threads of the consuming kernel read neighbouring words:   Ssuf [g][K][n]      Ppre [g][K+1][n+1]
 template <typename S> struct Tables {
@@ -426,8 +444,10 @@ SMCPP_HD void csfs_emit(const CsfsCtx<S> &c, int t, int nt) {
         const double v = sval(e);
         if (c.po.flags) {
             if (!(v > 0.0) || v > 1.0) c.po.flags[0] = 1;
-            else if (c.ps.maxspan && (double)c.ps.maxspan[k] * ::log(v) < -450.0) c.po.flags[2] = 1;
+            else if (c.ps.maxspan && (double)c.ps.maxspan[k] * ::log(v) < SS_SPAN_LOG_MIN) c.po.flags[2] = 1;
         }
+        if (c.dir == 0 && c.po.key_ok && c.ps.maxspan && c.ps.maxspan[k] > 1 && v > 0.0 && (double)c.ps.maxspan[k] * ::log(v) >= SS_SPAN_LOG_MAX)
+            c.po.key_ok[k] = 1;
         if (c.dir == 0) {
             c.po.Eg_v[(size_t)k * M + h] = v;
             const int kl = c.ps.local ? c.ps.local[k] : k;
