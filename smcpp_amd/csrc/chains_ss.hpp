@@ -764,6 +764,46 @@ __global__ __launch_bounds__(256) void k_ss_jump_tables(SsArgs a, int slot, floa
     if (lane == i) diag[i] = x[0];
 }
 
+// The n >= 0 scan positions of a row behind its first one.  They are n times the SAME step (one emission vector, one set of
+// constants), so how they are grouped moves no bit; what the grouping decides is how many TAKEN branches the row pays, and a wavefront
+// that is alone on its SIMD pays the refetch behind every one of them in full.  Four positions per trip of a
+// bottom-tested loop, then the n mod 4 left over as nested ifs, so that whichever of them ends the row is ONE branch to the end:
+// n / 4 - 1 back-edges, one skip of the loop where n < 4 and one of the nest where n mod 4 < 3 - at most ceil(n / 4) + 1 taken
+// branches, where two positions per trip and a trailing odd one spent n / 2 + 1.  Loops with ONE exit only: a second one (a break out
+// of the trip behind the row's last position) sends every exit through a block that tests which one it was.  (The DPP moves of a step
+// are convergent operations: the compiler unrolls none of this itself.)
+// At two and more states per lane the grouping is NOT free: a step there ends in multiplies and begins with adds over the lane's own
+// states, the compiler contracts the two where they meet inside one basic block, and the sums of c5 (M = 256) moved in their last
+// bits with four per trip.  Those instantiations keep the grouping they had - two per trip, then the odd one.
+template <int NPL, typename F>
+__device__ __forceinline__ void ss_positions(int n, F &&step) {
+    if constexpr (NPL > 1) {
+        int t = 0;
+        for (; t + 1 < n; t += 2) { step(); step(); }
+        if (t < n) step();
+    } else {
+        if (n >= 4) {
+            int q = n >> 2;
+            do { step(); step(); step(); step(); } while (--q > 0);
+        }
+        const int r = n & 3;
+        if (r >= 1) {
+            step();
+            if (r >= 2) {
+                step();
+                if (r == 3) step();
+            }
+        }
+    }
+}
+#define SS_INL_ __attribute__((always_inline))
+// The likelihood of a row test, told to the compiler at ONE state per lane only.  At two and more, where two steps meet inside one
+// basic block the compiler contracts across the seam, so there the loops keep the very shape they had - hints, exits and all (c5's
+// sums, M = 256, moved in their last bits with the new shape even at two positions per trip).
+// (macros: the hint has to stand in the branch's own condition - behind a call it is lowered before the call is inlined)
+#define SS_RARE_(c) (NPL == 1 ? (bool)__builtin_expect((bool)(c), 0) : (bool)(c))
+#define SS_USUAL_(c) (NPL == 1 ? (bool)__builtin_expect((bool)(c), 1) : (bool)(c))
+
 // (JMP: the instantiation whose row loop tests for jump rows - chosen per launch, so that an input that never jumps runs the loops it had)
 template <int NPL, bool ALLLDS, bool JMP = false>
 __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double *sE, long long base, int first, int last, int lane, float (&x)[NPL]);
@@ -796,7 +836,7 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
     // below with its stores off - so that the vector at r0 is the neighbour's end vector to the certificate's tolerance
     const bool halo = !RERUN && !HYB && a.halo && ch.h0 < ch.r0;
     const int rbeg = halo ? ch.h1 : ch.r0;
-    const int jst = ch.r0 - rbeg;                  // the iteration that finishes row r0 (0 without a halo)
+    int jst = ch.r0 - rbeg;                        // the iteration that finishes row r0 (0 without a halo)
     if (halo && ch.h0 < ch.h1) {
         float xf[NPL];
 #pragma unroll
@@ -877,6 +917,11 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
     const long long t0c = __builtin_readcyclecounter(), t0r = __builtin_amdgcn_s_memrealtime();
     long long npos = 0;
     ss_vm_drain();
+    // (ONE exit and no way round the row's tail: a merge puts j on the last row and jst behind it, which turns the stores of the
+    // step it still takes off, and leaves through the loop's own test - a break is a second exit, and the compiler then sends every
+    // row through a block that tells the two apart: a taken branch per row.  What a row rarely does - the merge test of
+    // every 16th row, the flush of every 64th, the halo's rows, the further positions of a row of span > 1 - is marked unlikely, so
+    // that it lies out of line and a span-1 row falls through to the back-edge; ss_positions has the arithmetic of the branches.)
     for (int j = 0; j < nrows; ++j) {
         const int jl = j & 63;
         // this row's descriptor, the next row's, and the request for the one behind it
@@ -886,7 +931,9 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
         const int ekr = (d0.x >> 16) & 0xFF;
         const float flo = NPL >= 2 ? ss_floor_of<NPL>(d0.x) : 1e-10f;   // floor of the vector stored where this row begins
         npos += span;
-        if (MIX && jl == 0 && j > 0) cflush(j - 1);
+        // (the empty statement keeps the row test a scalar branch of its own: folded into the lanes' store mask it is an
+        // exec-mask skip that 63 rows of 64 take)
+        if (MIX && __builtin_expect(jl == 0 && j > 0, 0)) { asm volatile(""); cflush(j - 1); }
         // emission vector of the next row
         const int slot_n = d1.x & 0xFFFF;
         double en[NPL];
@@ -904,7 +951,7 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
                         const float old = arow[(size_t)j * Mp + st[0]];
                         if (!(fabsf(an - old) <= a.eps_f * fabsf(old))) bad = true;
                     }
-                    if (!__any(bad)) { merged = true; break; }
+                    if (!__any(bad)) { merged = true; j = nrows - 1; continue; }
                 }
                 if (stor[0]) arow[(size_t)j * Mp + st[0]] = an;
                 if (lane == 0) crow[j] = S;
@@ -933,7 +980,7 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
         double fb[NPL];
 #pragma unroll
         for (int k = 0; k < NPL; ++k) fb[k] = 0.0;
-        if (j > 0) {
+        if (SS_USUAL_(j > 0)) {
             float an[NPL];
 #pragma unroll
             for (int k = 0; k < NPL; ++k) {
@@ -941,7 +988,7 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
                 an[k] = live[k] ? fmaxf((float)xs, flo) : 0.f;
                 fb[k] = (double)an[k] - xs;
             }
-            if (RERUN && !a.full_f && (j & 15) == 0 && j >= 16) {
+            if (RERUN && SS_RARE_(!a.full_f && (j & 15) == 0 && j >= 16)) {
                 bool bad = false;
 #pragma unroll
                 for (int k = 0; k < NPL; ++k)
@@ -949,9 +996,13 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
                         const float old = MIX ? *ap[k] : arow[(size_t)j * Mp + st[k]];
                         if (!(fabsf(an[k] - old) <= a.eps_f * fabsf(old))) bad = true;
                     }
-                if (!__any(bad)) { merged = true; if (MIX) cflush(j - 1); break; }
+                if (!__any(bad)) {
+                    merged = true;
+                    if (MIX) cflush(j - 1);
+                    if constexpr (NPL == 1) { j = nrows - 1; jst = nrows; } else break;
+                }
             }
-            if (j > jst) {
+            if (SS_USUAL_(j > jst)) {
                 if (MIX) {
 #pragma unroll
                     for (int k = 0; k < NPL; ++k) if (stor[k]) *ap[k] = an[k];
@@ -961,8 +1012,12 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
                     for (int k = 0; k < NPL; ++k) if (stor[k]) arow[(size_t)j * Mp + st[k]] = an[k];
                     if (lane == 0) crow[j] = S;
                 }
-            } else if (j == jst) {
-                // (halo only: row r0 belongs to the neighbour; what this chunk starts from is what the certificate compares)
+            } else if (NPL > 1 && j == jst) {
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) if (stor[k]) a.used_f[(size_t)c * Mp + st[k]] = an[k];
+            }
+            if (NPL == 1 && halo && __builtin_expect(j == jst, 0)) {
+                // (row r0 belongs to the neighbour; what this chunk starts from is what the certificate compares)
 #pragma unroll
                 for (int k = 0; k < NPL; ++k) if (stor[k]) a.used_f[(size_t)c * Mp + st[k]] = an[k];
             }
@@ -974,24 +1029,13 @@ __device__ __forceinline__ void ss_forward_wave(const SsArgs &a, const double *s
             if (span == 1) { const double edf = (double)(float)ed; y[k] = __builtin_fma(edf - ed, x[k], y[k]); ed = edf; }
             x[k] = __builtin_fma(ed, fb[k], y[k] * inv);
         }
-        {
-            // two positions per trip (the DPP moves are convergent operations: the compiler will not unroll this loop itself)
-            double S2;
-            int t = 1;
-            for (; t + 1 < span; t += 2) {
+        if (NPL > 1 || __builtin_expect(span > 1, 0))
+            ss_positions<NPL>(span - 1, [&]() SS_INL_ {
+                double S2;
                 ss_fwd_step<NPL, MIX, MIX && H32>(cst, x, e, y, S2);
 #pragma unroll
                 for (int k = 0; k < NPL; ++k) x[k] = y[k];
-                ss_fwd_step<NPL, MIX, MIX && H32>(cst, x, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) x[k] = y[k];
-            }
-            if (t < span) {
-                ss_fwd_step<NPL, MIX, MIX && H32>(cst, x, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) x[k] = y[k];
-            }
-        }
+            });
 #pragma unroll
         for (int k = 0; k < NPL; ++k) e[k] = en[k];
         if (MIX) {
@@ -1051,7 +1095,7 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
     // stores off; at row r1 the vector is normalised (as a chunk's end vector is) and becomes what the certificate compares
     const bool halo = !RERUN && !HYB && a.halo && ch.h0 > ch.r1;
     const int rend = halo ? ch.h1 : ch.r1;
-    const int jst = rend - ch.r1;
+    int jst = rend - ch.r1;
     if (halo && ch.h0 > ch.h1) {
         float bf_[NPL];
 #pragma unroll
@@ -1120,7 +1164,7 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
         double en[NPL];
         ss_emission<NPL, true, ALLLDS>(a, sE, slot_n, lane, en);
         // beta[ell] in the running scale (hmm.cpp:142 renormalises; every consumer is invariant to a per-row scale)
-        if (RERUN && !a.full_b && (j & 15) == 0 && j >= 16) {
+        if (RERUN && SS_RARE_(!a.full_b && (j & 15) == 0 && j >= 16)) {
             bool bad = false;
 #pragma unroll
             for (int k = 0; k < NPL; ++k)
@@ -1128,9 +1172,12 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
                     const double old = MIX ? *bp[k] : brow[-(ptrdiff_t)j * Mp + st[k]];
                     if (!(fabs(b[k] - old) <= a.eps_b * fabs(old))) bad = true;
                 }
-            if (!__any(bad)) { merged = true; break; }
+            if (!__any(bad)) {
+                merged = true;
+                if constexpr (NPL == 1) { j = nrows - 1; jst = nrows; } else break;
+            }
         }
-        if (halo && j == jst) {
+        if (halo && SS_RARE_(j == jst)) {
             // the halo has reached row r1: normalised like a chunk's end vector - the start vector of this chunk's own rows
             double part = 0.0;
 #pragma unroll
@@ -1142,7 +1189,7 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
                 if (stor[k]) a.used_b[(size_t)c * Mp + st[k]] = b[k];
             }
         }
-        if (j >= jst) {
+        if (SS_USUAL_(j >= jst)) {
 #pragma unroll
             for (int k = 0; k < NPL; ++k) if (stor[k]) { if (MIX) *bp[k] = b[k]; else brow[-(ptrdiff_t)j * Mp + st[k]] = b[k]; }
         }
@@ -1162,24 +1209,13 @@ __device__ __forceinline__ void ss_backward_wave(const SsArgs &a, const double *
         const double inv = (double)__builtin_amdgcn_rcpf(Sw);
 #pragma unroll
         for (int k = 0; k < NPL; ++k) b[k] = y[k] * inv;
-        {
-            // two positions per trip (the DPP moves are convergent operations: the compiler will not unroll this loop itself)
-            float S2;
-            int t = 1;
-            for (; t + 1 < span; t += 2) {
+        if (NPL > 1 || __builtin_expect(span > 1, 0))
+            ss_positions<NPL>(span - 1, [&]() SS_INL_ {
+                float S2;
                 ss_bwd_step<NPL, MIX, MIX && H32>(cst, b, e, y, S2);
 #pragma unroll
                 for (int k = 0; k < NPL; ++k) b[k] = y[k];
-                ss_bwd_step<NPL, MIX, MIX && H32>(cst, b, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) b[k] = y[k];
-            }
-            if (t < span) {
-                ss_bwd_step<NPL, MIX, MIX && H32>(cst, b, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) b[k] = y[k];
-            }
-        }
+            });
 #pragma unroll
         for (int k = 0; k < NPL; ++k) e[k] = en[k];
         if (MIX) {
@@ -1370,6 +1406,75 @@ __device__ __forceinline__ void ss_emission_f(const SsArgs &a, const double *sE,
     for (int k = 0; k < NPL; ++k) e[k] = (float)ed[k];
 }
 
+// The row loop of the four light walks (BWD: the backward chain's steps and descriptors walked downwards): `v` is the vector at the
+// row the walk starts from, `e` the emission vector of its first row, d1 / d2 the first two descriptors (ss_desc_first), `rd` the
+// stream behind them.
+// Two loops, for the branches a row takes (ss_positions): the inner one runs through span-1 rows - 55 % of the headline's - and its
+// bottom test is the ONE branch such a row takes; it ends, by falling through, behind the first position of a row of span > 1, whose
+// other positions follow in line with that row's emission vector (`ep`: `e` has moved on to the next row's), and the outer
+// back-edge is that row's only branch beside those of its positions.  One exit per loop - the span test and the row count are ONE
+// condition.  The walk's last row leaves the inner loop whatever its span, so span - t = 0 positions is a case of ss_positions.
+template <int NPL, bool BWD, bool ALLLDS, bool H32, bool JMP>
+__device__ __forceinline__ void ss_light_walk(const SsArgs &a, const double *sE, SsDescStream rd, ss_desc_t d1, ss_desc_t d2, int nrows,
+                                              int lane, const SsLightC<NPL> &cst, const SsJumpR &jr, float (&e)[NPL], float (&v)[NPL]) {
+    auto step = [&](const float (&em)[NPL], float (&y)[NPL], float &S) SS_INL_ {
+        if constexpr (BWD) ss_bwd_step_f<NPL, H32>(cst, v, em, y, S);
+        else ss_fwd_step_f<NPL, H32>(cst, v, em, y, S);
+    };
+    if constexpr (NPL > 1) {
+        // (the one-level loop these instantiations had: SS_RARE_)
+        for (int j = 0; j < nrows; ++j) {
+            const ss_desc_t d0 = d1;
+            d1 = d2; d2 = ss_desc_fetch<BWD ? -1 : 1>(rd, d1.x);
+            const int span = d0.y;
+            const int slot_n = d1.x & 0xFFFF;
+            float en[NPL], y[NPL], S;
+            ss_emission_f<NPL, BWD, ALLLDS>(a, sE, slot_n, lane, en);
+            step(e, y, S);
+            const float inv = __builtin_amdgcn_rcpf(S);
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) v[k] = y[k] * inv;
+            ss_positions<NPL>(span - 1, [&]() SS_INL_ {
+                float S2;
+                step(e, y, S2);
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) v[k] = y[k];
+            });
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) e[k] = en[k];
+        }
+        return;
+    }
+    int j = 0;
+    while (j < nrows) {
+        int span;
+        bool jrow;
+        float ep[NPL], y[NPL];
+        do {
+            const ss_desc_t d0 = d1;
+            d1 = d2; d2 = ss_desc_fetch<BWD ? -1 : 1>(rd, d1.x);
+            span = d0.y;
+            jrow = JMP && (d0.x & SS_ROW_JUMP);          // marked rows are the minority
+            const int slot_n = d1.x & 0xFFFF;
+            float en[NPL], S;
+            ss_emission_f<NPL, BWD, ALLLDS>(a, sE, slot_n, lane, en);
+            step(e, y, S);
+            const float inv = __builtin_amdgcn_rcpf(S);
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) { v[k] = y[k] * inv; ep[k] = e[k]; e[k] = en[k]; }
+            ++j;
+        } while ((span == 1) & (j < nrows));
+        int t = 1;
+        if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, v[0], t, span); }
+        ss_positions<NPL>(span - t, [&]() SS_INL_ {
+            float S2;
+            step(ep, y, S2);
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) v[k] = y[k];
+        });
+    }
+}
+
 // float, store-free steps of the forward chain over rows first+1 .. last of the contig at `base`: x on entry = the vector at row
 // `first`, on return the (un-normalised) vector at row `last`.  The halo of a first pass (ss_forward_wave).
 template <int NPL, bool ALLLDS, bool JMP>
@@ -1387,37 +1492,7 @@ __device__ __forceinline__ void ss_fwd_light_rows(const SsArgs &a, const double 
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<false>(a, lane, jr);
     ss_vm_drain();
-    for (int j = 0; j < nrows; ++j) {
-        const ss_desc_t d0 = d1;
-        d1 = d2; d2 = ss_desc_fetch<1>(rd, d1.x);
-        const int span = d0.y;
-        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
-        const int slot_n = d1.x & 0xFFFF;
-        float en[NPL], y[NPL], S;
-        ss_emission_f<NPL, false, ALLLDS>(a, sE, slot_n, lane, en);
-        ss_fwd_step_f<NPL>(cst, x, e, y, S);
-        const float inv = __builtin_amdgcn_rcpf(S);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) x[k] = y[k] * inv;
-        float S2;
-        int t = 1;
-        if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, x[0], t, span); }
-        for (; t + 1 < span; t += 2) {
-            ss_fwd_step_f<NPL>(cst, x, e, y, S2);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) x[k] = y[k];
-            ss_fwd_step_f<NPL>(cst, x, e, y, S2);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) x[k] = y[k];
-        }
-        if (t < span) {
-            ss_fwd_step_f<NPL>(cst, x, e, y, S2);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) x[k] = y[k];
-        }
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) e[k] = en[k];
-    }
+    ss_light_walk<NPL, false, ALLLDS, false, JMP>(a, sE, rd, d1, d2, nrows, lane, cst, jr, e, x);
 }
 // ... and of the backward chain over rows rhi .. rlo+1 (b on entry = the vector at row rhi, on return at row rlo)
 template <int NPL, bool ALLLDS, bool JMP>
@@ -1435,37 +1510,7 @@ __device__ __forceinline__ void ss_bwd_light_rows(const SsArgs &a, const double 
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<true>(a, lane, jr);
     ss_vm_drain();
-    for (int j = 0; j < nrows; ++j) {
-        const ss_desc_t d0 = d1;
-        d1 = d2; d2 = ss_desc_fetch<-1>(rd, d1.x);
-        const int span = d0.y;
-        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
-        const int slot_n = d1.x & 0xFFFF;
-        float en[NPL], y[NPL], Sw;
-        ss_emission_f<NPL, true, ALLLDS>(a, sE, slot_n, lane, en);
-        ss_bwd_step_f<NPL>(cst, b, e, y, Sw);
-        const float inv = __builtin_amdgcn_rcpf(Sw);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) b[k] = y[k] * inv;
-        float S2;
-        int t = 1;
-        if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, b[0], t, span); }
-        for (; t + 1 < span; t += 2) {
-            ss_bwd_step_f<NPL>(cst, b, e, y, S2);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) b[k] = y[k];
-            ss_bwd_step_f<NPL>(cst, b, e, y, S2);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) b[k] = y[k];
-        }
-        if (t < span) {
-            ss_bwd_step_f<NPL>(cst, b, e, y, S2);
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) b[k] = y[k];
-        }
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) e[k] = en[k];
-    }
+    ss_light_walk<NPL, true, ALLLDS, false, JMP>(a, sE, rd, d1, d2, nrows, lane, cst, jr, e, b);
 }
 
 template <int NPL, bool ALLLDS, bool H32 = false, bool JMP = false>
@@ -1496,40 +1541,7 @@ __device__ __forceinline__ void ss_forward_light(const SsArgs &a, const double *
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<false>(a, lane, jr);
     ss_vm_drain();
-    for (int j = 0; j < nrows; ++j) {
-        const ss_desc_t d0 = d1;
-        d1 = d2; d2 = ss_desc_fetch<1>(rd, d1.x);
-        const int span = d0.y;
-        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
-        const int slot_n = d1.x & 0xFFFF;
-        float en[NPL], y[NPL], S;
-        ss_emission_f<NPL, false, ALLLDS>(a, sE, slot_n, lane, en);
-        ss_fwd_step_f<NPL, H32>(cst, x, e, y, S);
-        const float inv = __builtin_amdgcn_rcpf(S);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) x[k] = y[k] * inv;
-        {
-            // two positions per trip (the DPP moves are convergent operations: the compiler will not unroll this loop itself)
-            float S2;
-            int t = 1;
-            if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, x[0], t, span); }
-            for (; t + 1 < span; t += 2) {
-                ss_fwd_step_f<NPL, H32>(cst, x, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) x[k] = y[k];
-                ss_fwd_step_f<NPL, H32>(cst, x, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) x[k] = y[k];
-            }
-            if (t < span) {
-                ss_fwd_step_f<NPL, H32>(cst, x, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) x[k] = y[k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) e[k] = en[k];
-    }
+    ss_light_walk<NPL, false, ALLLDS, H32, JMP>(a, sE, rd, d1, d2, nrows, lane, cst, jr, e, x);
     float part = 0.f;
 #pragma unroll
     for (int k = 0; k < NPL; ++k) part += x[k];
@@ -1568,40 +1580,7 @@ __device__ __forceinline__ void ss_backward_light(const SsArgs &a, const double 
     jr.P = 0; jr.sh = 31;
     if constexpr (JMP) ss_jump_load<true>(a, lane, jr);
     ss_vm_drain();
-    for (int j = 0; j < nrows; ++j) {
-        const ss_desc_t d0 = d1;
-        d1 = d2; d2 = ss_desc_fetch<-1>(rd, d1.x);
-        const int span = d0.y;
-        const bool jrow = JMP && (d0.x & SS_ROW_JUMP);   // marked rows are the minority
-        const int slot_n = d1.x & 0xFFFF;
-        float en[NPL], y[NPL], Sw;
-        ss_emission_f<NPL, true, ALLLDS>(a, sE, slot_n, lane, en);
-        ss_bwd_step_f<NPL, H32>(cst, b, e, y, Sw);
-        const float inv = __builtin_amdgcn_rcpf(Sw);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) b[k] = y[k] * inv;
-        {
-            // two positions per trip (the DPP moves are convergent operations: the compiler will not unroll this loop itself)
-            float S2;
-            int t = 1;
-            if constexpr (JMP) { if (__builtin_expect(jrow, 0)) t = ss_jump_run(jr, b[0], t, span); }
-            for (; t + 1 < span; t += 2) {
-                ss_bwd_step_f<NPL, H32>(cst, b, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) b[k] = y[k];
-                ss_bwd_step_f<NPL, H32>(cst, b, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) b[k] = y[k];
-            }
-            if (t < span) {
-                ss_bwd_step_f<NPL, H32>(cst, b, e, y, S2);
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) b[k] = y[k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) e[k] = en[k];
-    }
+    ss_light_walk<NPL, true, ALLLDS, H32, JMP>(a, sE, rd, d1, d2, nrows, lane, cst, jr, e, b);
     float part = 0.f;
 #pragma unroll
     for (int k = 0; k < NPL; ++k) part += live[k] ? b[k] : 0.f;

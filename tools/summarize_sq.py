@@ -13,10 +13,14 @@ from collections import defaultdict
 
 def main(src, out, workload):
     vals = defaultdict(lambda: defaultdict(list))
-    for f in glob.glob(f"{src}/p*/*/*counter_collection.csv"):
+    for f in sorted(glob.glob(f"{src}/p*/*/*counter_collection.csv")):
+        one = defaultdict(lambda: defaultdict(list))
         for r in csv.DictReader(open(f)):
-            name = r["Kernel_Name"].split("(")[0]
-            vals[name][r["Counter_Name"]].append(float(r["Counter_Value"]))
+            one[r["Kernel_Name"].split("(")[0]][r["Counter_Name"]].append(float(r["Counter_Value"]))
+        for name, cs in one.items():
+            for c, v in cs.items():
+                if c not in vals[name]:           # a counter that several passes collect is taken from the first of them
+                    vals[name][c] = v
     n_esteps = max([len(next(iter(v.values()))) for k, v in vals.items() if "k_loglik_final" in k] + [1])
     res = {"note": "rocprofv3 --kernel-trace --pmc <set> (one pass per set), python bench.py --no-cpu --workload %s --steps 3 --warmup 1; "
                    "per_step = sum over all launches of the kernel in the run / E-steps of the run" % workload,
